@@ -7,8 +7,14 @@ recall@10".  One step = one batch of B synthetic queries per rank through the wh
   100 candidates per query at S_pair=128  ->  top-10.
 Weights are seeded random (no checkpoints offline), inputs synthetic.
 
-Launch: python bench.py [--gpus N --steps K --warmup W].  Under torch.distributed.run (WORLD_SIZE
-set) every process is one rank on one GPU (RCCL); run directly with --gpus N > 1 the script
+A plain run sets up, runs W warmup and K timed steps and prints the line (value, ms_per_step, the
+timed region's stage times, kernel table and rooflines); --dump-outputs DIR also writes the last
+timed step's results as .npy files.  --full adds what takes runs of its own: recall@10, measured
+peaks, B = 32 search, fp8 / ranking fidelity, the drop-in route, the CPU baseline, the config5 and
+v2m3 fields (null in a plain line).
+
+Launch: python bench.py [--gpus N --steps K --warmup W] [--full].  Under torch.distributed.run
+(WORLD_SIZE set) every process is one rank on one GPU (RCCL); run directly with --gpus N > 1 the script
 starts the N ranks itself through torch.distributed.run before anything touches the GPU, waits for
 them and exits with the first non-zero rank status.  Rank 0 prints one JSON line.
 """
@@ -53,9 +59,21 @@ def parse():
     ap.add_argument("--passage-len", type=int, default=94)
     ap.add_argument("--embed-model", default="bge-base-en")
     ap.add_argument("--rerank-model", default="bge-reranker-base")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check everything beside the "
+                         "headline: recall@10, measured peaks, B = 32 search, fp8 and ranking "
+                         "fidelity, the drop-in route, the CPU baseline, the config5 and v2m3 "
+                         "fields (--no-cpu-baseline / --no-extras prune it).  Without it the run "
+                         "sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (PipelineResult: rows, logits, "
+                         "cand_rows, cand_sims) as DIR/<name>.npy (float64 row ids, float32 scores; "
+                         "DIR/<name>_rank<r>.npy at N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full: skip the cpu_baseline field")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip recall@10 and the measured peaks (A/B timing runs only)")
+                    help="--full: skip recall@10, the measured peaks and the other extra fields "
+                         "(A/B timing runs only)")
     ap.add_argument("--rerank-max-tokens", type=int, default=1638400,
                     help="cross-encoder tokens per chunk (workspace ~15 KB per token; 1,638,400 = "
                          "2 chunks per step: +0.8 %% over 524,288, profiles/r02_ab_chunks.log)")
@@ -111,6 +129,8 @@ def parse():
                          "bge-reranker-v2-m3 (the reranker the reference seeds; 24 layers, 1024-d) "
                          "in fp16 and in fp8 mode 3, after the config5 field (0 = skip)")
     a = ap.parse_args()
+    if not a.full:   # a plain run: the headline's steps only
+        a.no_extras = a.no_cpu_baseline = True
     if a.workload == "config5":
         as_config5(a)
         a.no_cpu_baseline = True
@@ -320,6 +340,8 @@ def run_bench(a, mp=None):
     p_tok, batches, pipe = W.p_tok, W.batches, W.pipe
     N_total, r0, r1, shard_p, setup_s, step_rows = W.N_total, W.r0, W.r1, W.shard_p, W.setup_s, W.step_rows
     dt, prof = timed_steps(W, a, world, dev, dist)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, W.last, rank, world)
     queries = world * a.batch * a.steps
     value = queries / dt
     stage_ms = dict(W.stage_ms, note=("HIP events on the launch stream at the stage boundaries "
@@ -344,7 +366,7 @@ def run_bench(a, mp=None):
 
     # ---- fp8 precision modes: final top-10 vs the fp16 reranker on the same candidates -----------
     fp8_fidelity = None
-    if a.fp8 and world == 1:
+    if a.fp8 and world == 1 and a.full:
         r8 = pipe.run(*batches[0])
         reranker.set_fp8(0)
         r16 = pipe.run(*batches[0])
@@ -807,7 +829,7 @@ def timed_steps(W, a, world, dev, dist):
         dist.barrier()
     t0 = time.perf_counter()
     for i in range(a.steps):
-        W.pipe.run(*W.batches[i % a.batches])
+        W.last = W.pipe.run(*W.batches[i % a.batches])
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -830,6 +852,19 @@ def timed_steps(W, a, world, dev, dist):
         dist.all_reduce(st, op=dist.ReduceOp.MAX)
         W.stage_ms = {k: round(float(v), 4) for k, v in zip(keys, st.tolist())}
     return dt, prof
+
+
+def dump_outputs(out_dir, res, rank=0, world=1):
+    """--dump-outputs: the PipelineResult of the last timed step as out_dir/<field>.npy (one file
+    per field; <field>_rank<r>.npy at N > 1): row ids in float64 (exact below 2^53), logits and
+    similarities in float32.  The inputs are seeded, so two builds run with the same arguments
+    can be compared file for file."""
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    for name, dtype in (("rows", np.float64), ("logits", np.float32),
+                        ("cand_rows", np.float64), ("cand_sims", np.float32)):
+        x = getattr(res, name).detach().cpu().numpy().astype(dtype)
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), x)
 
 
 def comm_record(dist, world, backend):

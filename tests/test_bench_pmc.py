@@ -5,6 +5,7 @@ import json
 import os
 import shutil
 
+import numpy as np
 import pytest
 
 import bench
@@ -112,6 +113,45 @@ def test_parse_defaults_and_config5_field_args(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py", "--workload", "config5"])
     c = bench.parse()
     assert c.embed_model == "bge-m3" and c.no_cpu_baseline
+
+
+def test_plain_run_skips_the_extras_and_full_restores_them(monkeypatch):
+    """A plain run measures the headline only; --full turns the extra fields back on, and
+    --no-extras / --no-cpu-baseline still prune a full run."""
+    import sys
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert not a.full and a.no_extras and a.no_cpu_baseline and a.dump_outputs is None
+    assert (a.steps, a.warmup) == (3, 1)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full"])
+    a = bench.parse()
+    assert a.full and not a.no_extras and not a.no_cpu_baseline
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-extras", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.no_extras and not a.no_cpu_baseline and a.dump_outputs == "d"
+
+
+def test_dump_outputs_writes_one_npy_per_field(tmp_path):
+    """--dump-outputs: rows / cand_rows as float64 (exact ids), logits / cand_sims as float32,
+    one file per field, per rank at N > 1."""
+    import torch
+    from super_rag_amd.pipeline import PipelineResult
+    rows = torch.tensor([[9_999_999, 3], [2 ** 40 + 1, 0]], dtype=torch.int64)
+    res = PipelineResult(rows, torch.tensor([[0.5, float("-inf")], [1.5, 2.5]]),
+                         torch.arange(6, dtype=torch.int64).view(2, 3),
+                         torch.linspace(0, 1, 6).view(2, 3))
+    out = tmp_path / "dump"
+    bench.dump_outputs(str(out), res)
+    assert sorted(os.listdir(out)) == ["cand_rows.npy", "cand_sims.npy", "logits.npy", "rows.npy"]
+    got = np.load(out / "rows.npy")
+    assert got.dtype == np.float64 and np.array_equal(got.astype(np.int64), rows.numpy())
+    lg = np.load(out / "logits.npy")
+    assert lg.dtype == np.float32 and lg[0, 0] == 0.5 and np.isneginf(lg[0, 1])
+    assert np.load(out / "cand_sims.npy").dtype == np.float32
+    assert np.load(out / "cand_rows.npy").dtype == np.float64
+    bench.dump_outputs(str(out), res, rank=1, world=2)
+    assert os.path.exists(out / "rows_rank1.npy")
 
 
 def test_dropin_procs_release_and_collect(tmp_path):

@@ -261,20 +261,38 @@ def test_two_rank_sharded_pipeline_equals_single_process():
             np.testing.assert_array_equal(got_hp[r][f], got_h[r][f])
 
 
-def test_bench_launches_its_own_ranks():
+def test_bench_launches_its_own_ranks(tmp_path):
     """`python bench.py --gpus 2` (no torch.distributed.run) starts both ranks itself; gloo lets
-    them share the box's one GPU.  The JSON line reports the world the backend formed."""
+    them share the box's one GPU.  The JSON line reports the world the backend formed, a plain
+    run leaves the --full fields null, and --dump-outputs writes each rank's last step."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    dump = tmp_path / "dump"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2",
                         "--dist-backend", "gloo", "--corpus-rows", "200000", "--batch", "32",
                         "--steps", "1", "--warmup", "1", "--batches", "1", "--no-cpu-baseline",
-                        "--rerank-max-tokens", "65536"],
+                        "--rerank-max-tokens", "65536", "--dump-outputs", str(dump)],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["config"]["global_batch"] == 64
     assert "reports world_size 2" in r.stderr
+    assert line["steps"] == 1 and line["ms_per_step"] > 0
+    # q/s x seconds per step = the step's 64 queries, within the line's rounding (2 and 3 decimals)
+    tol = 0.005 * line["ms_per_step"] / 1e3 + line["value"] * 0.0005 / 1e3 + 1e-6
+    assert abs(line["value"] * line["ms_per_step"] / 1e3 - 64) <= tol
+    assert all(line[f] is None for f in ("measured_peaks", "rerank_fidelity", "drop_in",
+                                         "cpu_baseline", "config5", "v2m3"))
+    for rank in (0, 1):
+        rows = np.load(dump / f"rows_rank{rank}.npy")
+        logits = np.load(dump / f"logits_rank{rank}.npy")
+        cand = np.load(dump / f"cand_rows_rank{rank}.npy")
+        sims = np.load(dump / f"cand_sims_rank{rank}.npy")
+        assert rows.dtype == cand.dtype == np.float64 and logits.dtype == sims.dtype == np.float32
+        assert rows.shape == logits.shape == (32, 10) and cand.shape == sims.shape == (32, 100)
+        assert ((rows >= 0) & (rows < 200000)).all() and np.isfinite(logits).all()
+        assert (np.diff(logits, axis=1) <= 0).all() and (np.diff(sims, axis=1) <= 0).all()
+        assert all(set(rows[i]) <= set(cand[i]) for i in range(32))
