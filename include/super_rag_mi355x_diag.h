@@ -36,6 +36,16 @@ int sr_diag_gemm(int variant, int epi, const void* X, int64_t lda, const void* W
                  const void* R, int64_t ldr, void* Y, int64_t ldy, int M, int N, int K, int device,
                  void* stream);
 
+/* Diagnostic: sr_diag_gemm on the 128x128 kernel the way the embedders call it (Encoder::forward's
+ * lin): with a lent workspace ws of ws_bytes on the device, so the K-steps are summed in chunks of
+ * 6 and, when the host heuristic of launch_gemm_variant splits (>= 2 chunks, <= 128 tiles,
+ * chunks x tiles x 64 KiB <= ws_bytes), the chunk groups run in separate workgroups that store
+ * partial tiles to ws and gemm_chunk_reduce_kernel finishes the tile.  Arguments and epilogues as
+ * sr_diag_gemm; variant is ignored apart from | 0x100 (split weights): the 128x128 kernel always. */
+int sr_diag_gemm_chunked(int variant, int epi, const void* X, int64_t lda, const void* W,
+                         const float* bias, const void* R, int64_t ldr, void* Y, int64_t ldy, int M,
+                         int N, int K, void* ws, int64_t ws_bytes, int device, void* stream);
+
 /* Diagnostic: the LayerNorm-folded FFN1 GEMM Y = 2 GELU(rstd_m (X W^T - mu_m colsum) + bias) on
  * device buffers (the cross-encoders' FFN1 epilogue), fp16 (f8 = 0: X M x K, W N x K fp16, Y fp16)
  * or fp8 (f8 = 1: X, W OCP e4m3 bytes, wexp the E8M0 exponent byte of each W row, Y e4m3 bytes);

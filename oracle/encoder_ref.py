@@ -78,13 +78,25 @@ def _fold8(u, g, beta, wt, bias, eps):
     return rstd * (e4m3(u.half().float()) @ wq.T - mu * wq.sum(1)) + (wt @ beta + bias)
 
 
+def _r16(x: torch.Tensor) -> torch.Tensor:
+    """x rounded to fp16 (nearest even), back in its own dtype."""
+    return x.half().to(x.dtype)
+
+
 def encode_hidden(cfg: RefConfig, w: dict, ids, mask, type_ids=None,
-                  fp8_ffn: bool = False, fp8: int = 0) -> torch.Tensor:
-    """Final hidden states [B, S, d] in fp32.  fp8 (the library's opt-in precision modes;
+                  fp8_ffn: bool = False, fp8: int = 0, fp16_operands: bool = False) -> torch.Tensor:
+    """Final hidden states [B, S, d] in the dtype of the weights (numpy weights: fp32; float64
+    torch tensors give the fp64 reference).  fp8 (the library's opt-in precision modes;
     fp8_ffn=True is fp8=1): 1 = the FFN activations 2 GELU(.) rounded to e4m3 and multiplied by
     fp8_rows(fp16(W2 / 2)); 2 = also FFN1 and the QKV of layers >= 1 as _fold8 on the pre-LN
-    residual sums; 3 = FFN1 as in 2, QKV in fp16 (super-rag_amd/csrc/encoder.cpp ffn1_8 / qkv_8)."""
+    residual sums; 3 = FFN1 as in 2, QKV in fp16 (super-rag_amd/csrc/encoder.cpp ffn1_8 / qkv_8).
+    fp16_operands (fp8 = 0 only) restates the rounding points of the fp32-residual embedders with
+    unsplit weights: the word / position / type embedding tables, every GEMM's weight and input
+    activation, q / k / v and the softmax probabilities are rounded to fp16; accumulation, biases,
+    the residual stream and the LayerNorms stay in the working dtype."""
     fp8 = max(fp8, 1 if fp8_ffn else 0)
+    assert not (fp16_operands and fp8), "fp16_operands restates the fp16 path (fp8 = 0)"
+    r16 = _r16 if fp16_operands else (lambda t: t)
     # weights given as torch tensors on a device (e.g. fp32 on the GPU for the long-sequence
     # checks) run the same restatement there; numpy weights run on the CPU
     dev = _t(w, "embeddings.word_embeddings.weight").device
@@ -94,9 +106,9 @@ def encode_hidden(cfg: RefConfig, w: dict, ids, mask, type_ids=None,
     tt = torch.zeros_like(ids) if type_ids is None else \
         torch.as_tensor(np.asarray(type_ids), dtype=torch.long, device=dev)
     pos = position_ids(ids, cfg.position_offset)
-    x = (_t(w, "embeddings.word_embeddings.weight")[ids]
-         + _t(w, "embeddings.position_embeddings.weight")[pos]
-         + _t(w, "embeddings.token_type_embeddings.weight")[tt])
+    x = (r16(_t(w, "embeddings.word_embeddings.weight")[ids])
+         + r16(_t(w, "embeddings.position_embeddings.weight")[pos])
+         + r16(_t(w, "embeddings.token_type_embeddings.weight")[tt]))
     h = _ln(x, _t(w, "embeddings.LayerNorm.weight"), _t(w, "embeddings.LayerNorm.bias"), cfg.ln_eps)
     d, H = cfg.hidden, cfg.heads
     dh = d // H
@@ -104,7 +116,7 @@ def encode_hidden(cfg: RefConfig, w: dict, ids, mask, type_ids=None,
     for l in range(cfg.layers):
         p = f"encoder.layer.{l}."
         def lin(x, n):
-            return x @ _t(w, p + n + ".weight").T + _t(w, p + n + ".bias")
+            return r16(x) @ r16(_t(w, p + n + ".weight")).T + _t(w, p + n + ".bias")
         if fp8 == 2 and l > 0:
             pp = f"encoder.layer.{l - 1}.output.LayerNorm."
             wqkv = torch.cat([_t(w, p + f"attention.self.{n}.weight") for n in ("query", "key", "value")])
@@ -113,11 +125,12 @@ def encode_hidden(cfg: RefConfig, w: dict, ids, mask, type_ids=None,
                              cfg.ln_eps).split(d, dim=-1)
         else:
             q, k, v = lin(h, "attention.self.query"), lin(h, "attention.self.key"), lin(h, "attention.self.value")
+            q, k, v = r16(q), r16(k), r16(v)
         q = q.reshape(B, S, H, dh).transpose(1, 2)
         k = k.reshape(B, S, H, dh).transpose(1, 2)
         v = v.reshape(B, S, H, dh).transpose(1, 2)
         s = q @ k.transpose(-1, -2) / math.sqrt(dh) + bias
-        ctx = (s.softmax(-1) @ v).transpose(1, 2).reshape(B, S, d)
+        ctx = (r16(s.softmax(-1)) @ v).transpose(1, 2).reshape(B, S, d)
         u1 = lin(ctx, "attention.output.dense") + h
         g1, b1 = _t(w, p + "attention.output.LayerNorm.weight"), _t(w, p + "attention.output.LayerNorm.bias")
         h = _ln(u1, g1, b1, cfg.ln_eps)
@@ -137,9 +150,8 @@ def encode_hidden(cfg: RefConfig, w: dict, ids, mask, type_ids=None,
 
 
 @torch.no_grad()
-def embed(cfg: RefConfig, w: dict, ids, mask, type_ids=None, pool: str = "cls") -> np.ndarray:
-    """Sentence embeddings [B, d], pooled then L2-normalised (fp32)."""
-    h = encode_hidden(cfg, w, ids, mask, type_ids)
+def pool_hidden(h: torch.Tensor, mask, pool: str = "cls") -> np.ndarray:
+    """Hidden states [B, S, d] -> sentence embeddings [B, d], pooled then L2-normalised."""
     m = torch.as_tensor(np.asarray(mask), dtype=torch.float32, device=h.device)
     if pool == "cls":
         e = h[:, 0]
@@ -148,6 +160,14 @@ def embed(cfg: RefConfig, w: dict, ids, mask, type_ids=None, pool: str = "cls") 
     n = e.norm(dim=-1, keepdim=True)
     e = torch.where(n > 0, e / n, torch.zeros_like(e))
     return e.cpu().numpy()
+
+
+@torch.no_grad()
+def embed(cfg: RefConfig, w: dict, ids, mask, type_ids=None, pool: str = "cls",
+          fp16_operands: bool = False) -> np.ndarray:
+    """Sentence embeddings [B, d], pooled then L2-normalised (in the dtype of the weights)."""
+    return pool_hidden(encode_hidden(cfg, w, ids, mask, type_ids, fp16_operands=fp16_operands),
+                       mask, pool)
 
 
 @torch.no_grad()

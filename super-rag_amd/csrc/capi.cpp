@@ -818,6 +818,32 @@ int sr_diag_gemm(int variant, int epi, const void* X, int64_t lda, const void* W
   SR_API_END
 }
 
+int sr_diag_gemm_chunked(int variant, int epi, const void* X, int64_t lda, const void* W,
+                         const float* bias, const void* R, int64_t ldr, void* Y, int64_t ldy, int M,
+                         int N, int K, void* ws, int64_t ws_bytes, int device, void* stream) {
+  SR_API_BEGIN
+  SR_NONNULL(X);
+  SR_NONNULL(W);
+  SR_NONNULL(bias);
+  SR_NONNULL(Y);
+  SR_NONNULL(ws);
+  SR_CHECK(epi >= 0 && epi <= 4, "diag_gemm_chunked: epi must be 0..4");
+  SR_CHECK((epi != 2 && epi != 4) || R, "diag_gemm_chunked: residual epilogue needs R");
+  SR_CHECK(ws_bytes > 0, "diag_gemm_chunked: the workspace must not be empty");
+  sr::DeviceGuard g(device);
+  sr::LnFold lf;  // the embedders' lin(): chunked sums, split-K when the workspace holds the tiles
+  if (variant >= 0 && (variant & 0x100)) {
+    SR_CHECK(K % 128 == 0, "diag_gemm_chunked: split weights need K % 128 == 0");
+    lf.x_k = K / 2;
+  }
+  lf.chunk_ws = static_cast<float*>(ws);
+  lf.chunk_ws_bytes = ws_bytes;
+  sr::launch_gemm_variant(sr::GEMM_SMALL, epi, reinterpret_cast<const sr::half_t*>(X), lda,
+                          reinterpret_cast<const sr::half_t*>(W), bias, R, ldr, Y, ldy, M, N, K,
+                          reinterpret_cast<hipStream_t>(stream), &lf);
+  SR_API_END
+}
+
 int sr_diag_gemm_stats(const void* X, int64_t lda, const void* W, const float* bias, const void* R,
                        int64_t ldr, void* Y, int64_t ldy, int M, int N, int K, float* stat_out,
                        int device, void* stream) {

@@ -148,6 +148,9 @@ SIGNATURES = {
 DIAG_SIGNATURES = {
     "sr_diag_gemm": (c_int, [c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
                              c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p]),
+    "sr_diag_gemm_chunked": (c_int, [c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                     c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_void_p,
+                                     c_int64, c_int, c_void_p]),
     "sr_diag_ffn1": (c_int, [c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                              c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_void_p]),
     "sr_diag_attention": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,

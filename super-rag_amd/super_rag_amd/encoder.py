@@ -218,20 +218,36 @@ def random_weights(spec: ModelSpec, seed: int = 0, style: str = "test") -> dict:
     style="hf":   BERT initialisation (N(0, 0.02) matrices/embeddings, LN = (1, 0), biases 0).
     style="test": additionally randomises biases and LayerNorm affine terms so every parameter
                   path is exercised by the parity tests.
+    style="outlier": style="test" with outlier hidden dimensions as trained encoders have them:
+                  at 3 hidden dims chosen by the seed, every LayerNorm's gamma is x 20 and its
+                  beta moved away from zero by 1.0 in its own sign -- except the last layer's
+                  output LayerNorm, which stays plain so the pooled embedding is not reduced to
+                  three coordinates.
     """
     rng = np.random.default_rng(seed)
+    rand = style in ("test", "outlier")
     out = {}
     for name, shape in weight_shapes(spec).items():
         if name.endswith("LayerNorm.weight"):
             v = np.ones(shape, np.float32)
-            if style == "test":
+            if rand:
                 v += 0.1 * rng.standard_normal(shape, dtype=np.float32)
         elif name.endswith("LayerNorm.bias") or name.endswith(".bias"):
-            v = (0.02 * rng.standard_normal(shape, dtype=np.float32) if style == "test"
+            v = (0.02 * rng.standard_normal(shape, dtype=np.float32) if rand
                  else np.zeros(shape, np.float32))
         else:
             v = 0.02 * rng.standard_normal(shape, dtype=np.float32)
         out[name] = v
+    if style == "outlier":   # (its own generator: everything else equals style="test")
+        dims = np.random.default_rng([seed, 0x0071]).choice(spec.hidden, 3, replace=False)
+        last = f"encoder.layer.{spec.layers - 1}.output.LayerNorm."
+        for name in out:
+            if name.startswith(last):
+                continue
+            if name.endswith("LayerNorm.weight"):
+                out[name][dims] *= 20.0
+            elif name.endswith("LayerNorm.bias"):
+                out[name][dims] += np.where(out[name][dims] < 0, -1.0, 1.0).astype(np.float32)
     if spec.arch == "xlmr":
         out["embeddings.position_embeddings.weight"][spec.position_offset] = 0.0  # padding_idx row
     return out

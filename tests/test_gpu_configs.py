@@ -136,8 +136,9 @@ def test_config1_bge_small_ingest_1k_chunks_top5():
     es = MODELS["bge-small-en"]
     w = random_weights(es, 31, "hf")
     tok = Tokenizer(es)
-    svc = EmbeddingService("openai", "BAAI/bge-small-en", "", "", 10, encoder=Encoder(es, weights=w),
-                           tokenizer=tok, device_batch=128)
+    enc = Encoder(es, weights=w)
+    svc = EmbeddingService("openai", "BAAI/bge-small-en", "", "", 10, encoder=enc, tokenizer=tok,
+                           device_batch=128)
     rng = np.random.default_rng(32)
     words = [f"w{i}" for i in range(5000)]
     parts = [SimpleNamespace(content=" ".join(rng.choice(words, 126)), metadata={"name": f"c{i}.md"})
@@ -152,6 +153,10 @@ def test_config1_bge_small_ingest_1k_chunks_top5():
         t_ids, t_mask = tok.encode_batch([texts[i]])
         ref = R.embed(ref_config(es), w, t_ids, t_mask)[0]
         assert np.linalg.norm(stored[i] - ref) <= 4e-3        # fp16-stored row vs fp32 oracle
+        # and the encoder's fp32 output of the same chunk (bge-small, unsplit fp16 weights)
+        err = np.linalg.norm(enc.embed(t_ids, t_mask)[0] - ref)
+        print(f"config1 chunk {i}: ||embed fp32 - e_ref|| {err:.2e}")
+        assert err <= EMB_TOL
     q = stored[rng.choice(1000, 16, replace=False)] + 0.3 * rng.standard_normal((16, es.hidden)).astype(np.float32)
     got = [[h.metadata["source"] for h in conn.search(QueryWithEmbedding(query="q", top_k=5,
                                                                          embedding=v.tolist())).results]
