@@ -152,6 +152,54 @@ int sr_topk_merge_dev(const float* sims, const int64_t* rows, int P, int B, int 
                       float* out_sim, int64_t* out_rows, int device, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * MMR diversification (maximal marginal relevance; graphiti maximal_marginal_relevance,
+ * graphiti_core/search/search_utils.py:1884-1922).  All scores are similarities (higher is
+ * better).  For one query with unit candidate rows c_i (zero rows stay zero), rel_i = cos(q, c_i)
+ * and G_ij = c_i . c_j:
+ *   SR_MMR_ONEPASS  the reference function: score_i = lambda rel_i + (lambda - 1) m_i with
+ *                   m_i = max(0, max_{j != i} G_ij) (the reference's zero diagonal: a lone
+ *                   candidate or one with only negative similarities gets 0); order (score desc,
+ *                   candidate position asc); score < min_score dropped; first k_out kept.  Two exact
+ *                   duplicates both get m = 1: both are demoted.
+ *   SR_MMR_GREEDY   the classical iteration: S starts empty; every step picks the unselected i
+ *                   maximising lambda rel_i + (lambda - 1) max(0, max_{j in S} G_ij) (ties: lower
+ *                   position) and reports that value as its score; stops after k_out picks, when
+ *                   the candidates run out or when the best value is below min_score.  The first
+ *                   of two duplicates keeps its rank, the second is demoted.
+ * lambda in [0, 1], K (candidates per query) in [1, SR_MMR_MAX_CAND], k_out in [1, K]; anything
+ * else is SR_ERR_INVALID before any device call.  The Gram matrix is computed on the fp16 rows with
+ * fp32 accumulation by one workgroup per query (128 candidates: the 64 KiB fp32 matrix fits its LDS).
+ * ---------------------------------------------------------------------------------------------- */
+#define SR_MMR_ONEPASS 0
+#define SR_MMR_GREEDY 1
+#define SR_MMR_MAX_CAND 128
+
+/* Explicit vectors (graphiti's signature). q: B x dim, cand: B x K x dim host fp32,
+ * n_cand[b] <= K valid ones (NULL = K). out_index: positions into the candidate list
+ * (-1 past the end), out_score: -inf past the end. Blocking.  The query and the candidates are
+ * normalised to fp16 rows exactly as a store normalises the rows it is given. */
+int sr_mmr_rerank(const float* q, const float* cand, const int32_t* n_cand, int B, int K,
+                  int dim, float lambda, int mode, float min_score, int k_out,
+                  float* out_score, int32_t* out_index, int device);
+
+/* Candidates as sr_store_search_dev wrote them (rows carry row_offset, -1 = missing;
+ * cand_sims = rel). Device outputs B x k_out: MMR score, cosine of the kept row, row
+ * (+row_offset; -inf / -inf / -1 past the end). Asynchronous on stream. */
+int sr_store_mmr_dev(sr_store* s, const int64_t* cand_rows, const float* cand_sims, int B,
+                     int K, int64_t row_offset, float lambda, int mode, float min_score,
+                     int k_out, float* out_score, float* out_sim, int64_t* out_rows,
+                     void* stream);
+
+/* Scan top-k_cand (sr_store_search_sim semantics, allow may be NULL), then MMR, keep k.
+ * out_dist = 1 - cos of the kept rows (SeekDB's score), in MMR order (+inf past the end; out_score
+ * -inf, out_rows -1). Blocking.  Under the fp8 scan mode the candidates carry their exact fp16
+ * re-scored similarities and MMR reads the fp16 rows, as in the fp16 mode. */
+int sr_store_search_mmr(sr_store* s, const float* q, int B, int k, int k_cand,
+                        float lambda, int mode, float min_score, const uint8_t* allow,
+                        int64_t mask_key, float* out_score, float* out_dist,
+                        int64_t* out_rows);
+
+/* ------------------------------------------------------------------------------------------------
  * Lexical (BM25) index and hybrid dense + lexical retrieval  (BASELINE config 5)
  * The reference declares a `fulltext_search` node type (schema/view_models.py:276-283,
  * FulltextSearchParams{topk, keywords} at :1043-1047) and a merge slot for its output

@@ -256,6 +256,88 @@ int sr_store_search_dev(sr_store* s, const void* q, int q_dtype, int B, int k, f
   SR_API_END
 }
 
+// ---- MMR diversification (k_mmr.hip) -----------------------------------------------------------
+int sr_mmr_rerank(const float* q, const float* cand, const int32_t* n_cand, int B, int K, int dim,
+                  float lambda, int mode, float min_score, int k_out, float* out_score,
+                  int32_t* out_index, int device) {
+  SR_API_BEGIN
+  sr::mmr_check_args(B, K, k_out, lambda, mode);
+  SR_CHECK(dim > 0 && dim <= 8192, "mmr: dim must be in [1, 8192]");
+  if (B == 0) return SR_OK;
+  SR_NONNULL(q);
+  SR_NONNULL(cand);
+  SR_NONNULL(out_score);
+  SR_NONNULL(out_index);
+  sr::DeviceGuard g(device);
+  const int64_t ld = sr::round_up(dim, 64);
+  const int64_t nc = (int64_t)B * K, no = (int64_t)B * k_out;
+  // workspace: fp32 inputs | fp16 rows | n_cand | outputs (every part a multiple of 16 bytes)
+  const size_t b_q32 = (size_t)sr::round_up((int64_t)B * dim * 4, 16);
+  const size_t b_c32 = (size_t)sr::round_up(nc * dim * 4, 16);
+  const size_t b_q16 = (size_t)B * ld * 2, b_c16 = (size_t)nc * ld * 2;
+  const size_t b_n = (size_t)sr::round_up((int64_t)B * 4, 16), b_o = (size_t)sr::round_up(no * 4, 16);
+  sr::DevBuf ws;
+  ws.reserve(b_q32 + b_c32 + b_q16 + b_c16 + b_n + 2 * b_o);
+  char* w = ws.as<char>();
+  float* q32 = reinterpret_cast<float*>(w);
+  float* c32 = reinterpret_cast<float*>(w + b_q32);
+  sr::half_t* q16 = reinterpret_cast<sr::half_t*>(w + b_q32 + b_c32);
+  sr::half_t* c16 = reinterpret_cast<sr::half_t*>(w + b_q32 + b_c32 + b_q16);
+  int32_t* dn = reinterpret_cast<int32_t*>(w + b_q32 + b_c32 + b_q16 + b_c16);
+  float* ds = reinterpret_cast<float*>(w + b_q32 + b_c32 + b_q16 + b_c16 + b_n);
+  int32_t* di = reinterpret_cast<int32_t*>(w + b_q32 + b_c32 + b_q16 + b_c16 + b_n + b_o);
+  hipStream_t st = nullptr;
+  SR_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  try {
+    SR_HIP(hipMemcpyAsync(q32, q, (size_t)B * dim * 4, hipMemcpyHostToDevice, st));
+    SR_HIP(hipMemcpyAsync(c32, cand, (size_t)nc * dim * 4, hipMemcpyHostToDevice, st));
+    if (n_cand) SR_HIP(hipMemcpyAsync(dn, n_cand, (size_t)B * 4, hipMemcpyHostToDevice, st));
+    sr::launch_normalize_rows(q32, SR_DTYPE_F32, B, dim, q16, (int)ld, st);
+    sr::launch_normalize_rows(c32, SR_DTYPE_F32, nc, dim, c16, (int)ld, st);
+    sr::launch_mmr_rerank(c16, ld, nc, nullptr, 0, n_cand ? dn : nullptr, nullptr, q16, B, K, lambda,
+                          mode, min_score, k_out, ds, nullptr, di, nullptr, st);
+    SR_HIP(hipMemcpyAsync(out_score, ds, (size_t)no * 4, hipMemcpyDeviceToHost, st));
+    SR_HIP(hipMemcpyAsync(out_index, di, (size_t)no * 4, hipMemcpyDeviceToHost, st));
+    SR_HIP(hipStreamSynchronize(st));
+  } catch (...) {
+    (void)hipStreamSynchronize(st);
+    (void)hipStreamDestroy(st);
+    throw;
+  }
+  SR_HIP(hipStreamDestroy(st));
+  SR_API_END
+}
+
+int sr_store_mmr_dev(sr_store* s, const int64_t* cand_rows, const float* cand_sims, int B, int K,
+                     int64_t row_offset, float lambda, int mode, float min_score, int k_out,
+                     float* out_score, float* out_sim, int64_t* out_rows, void* stream) {
+  SR_API_BEGIN
+  SR_NONNULL(s);
+  sr::mmr_check_args(B, K, k_out, lambda, mode);
+  if (B == 0) return SR_OK;
+  SR_NONNULL(cand_rows);
+  SR_NONNULL(cand_sims);
+  SR_NONNULL(out_score);
+  SR_NONNULL(out_sim);
+  SR_NONNULL(out_rows);
+  std::lock_guard<std::mutex> lk(s->impl->mu);
+  s->impl->mmr_dev(cand_rows, cand_sims, B, K, row_offset, lambda, mode, min_score, k_out,
+                   out_score, out_sim, out_rows, reinterpret_cast<hipStream_t>(stream));
+  SR_API_END
+}
+
+int sr_store_search_mmr(sr_store* s, const float* q, int B, int k, int k_cand, float lambda,
+                        int mode, float min_score, const uint8_t* allow, int64_t mask_key,
+                        float* out_score, float* out_dist, int64_t* out_rows) {
+  SR_API_BEGIN
+  SR_NONNULL(s);
+  sr::mmr_check_args(B, k_cand, k, lambda, mode);
+  std::lock_guard<std::mutex> lk(s->impl->mu);
+  s->impl->search_mmr_host(q, B, k, k_cand, lambda, mode, min_score, allow, allow ? mask_key : 0,
+                           out_score, out_dist, out_rows);
+  SR_API_END
+}
+
 int sr_store_set_scan_dtype(sr_store* s, int dtype) {
   SR_API_BEGIN
   SR_NONNULL(s);

@@ -192,6 +192,20 @@ void launch_build_pairs(const int32_t* q_tok, const int32_t* q_len, int lq_max,
 void launch_rerank_select(const float* logits, int B, int K, int k_out, int32_t* out_index,
                           hipStream_t s);
 
+// k_mmr.hip — MMR diversification of K <= SR_MMR_MAX_CAND candidates per query (one workgroup
+// each).  Candidate i of query b is row cand_rows[b K + i] - row_offset of `rows` (cand_rows < 0 or a
+// row outside [0, n_rows): missing), or, with cand_rows null, row b K + i for i < n_cand[b] (null:
+// K).  rel [B][K] = cos(query, candidate), or null: computed from the normalised queries qn
+// [B][ld].  Outputs B x k_out in MMR order (-inf / -inf / -1 / -1 past the end): MMR score, rel of
+// the kept candidate (null: skipped), its position (null: skipped), its cand_rows entry (null:
+// skipped).  mmr_check_args throws SR_ERR_INVALID for arguments outside the documented limits.
+void mmr_check_args(int B, int K, int k_out, float lambda, int mode);
+void launch_mmr_rerank(const half_t* rows, int64_t ld, int64_t n_rows, const int64_t* cand_rows,
+                       int64_t row_offset, const int32_t* n_cand, const float* rel,
+                       const half_t* qn, int B, int K, float lambda, int mode, float min_score,
+                       int k_out, float* out_score, float* out_sim, int32_t* out_index,
+                       int64_t* out_rows, hipStream_t s);
+
 // k_lex.hip — reciprocal-rank fusion of two ranked row lists per query (-1 padded), fp64 scores.
 void launch_rrf_fuse(const int64_t* rows_a, int ka, const int64_t* rows_b, int kb, int B,
                      int rank_const, double min_score, int k_out, double* out_score,

@@ -87,6 +87,14 @@ class Store {
                    const uint8_t* allow = nullptr, int64_t mask_key = 0, bool raw_sim = false);
   void search_dev(const void* q, int q_dtype, int B, int k, float* out_sim, int64_t* out_rows,
                   int64_t row_offset, hipStream_t s, const uint8_t* elig = nullptr);
+  // MMR over candidates as search_dev wrote them (k_mmr.hip); asynchronous on s
+  void mmr_dev(const int64_t* cand_rows, const float* cand_sims, int B, int K, int64_t row_offset,
+               float lambda, int mode, float min_score, int k_out, float* out_score,
+               float* out_sim, int64_t* out_rows, hipStream_t s);
+  // search_host for the top k_cand, then MMR, keep k (out_dist = 1 - cos of the kept rows)
+  void search_mmr_host(const float* q, int B, int k, int k_cand, float lambda, int mode,
+                       float min_score, const uint8_t* allow, int64_t mask_key, float* out_score,
+                       float* out_dist, int64_t* out_rows);
   // device eligibility mask live & allow (cached per mask_key and store version); null for null
   const uint8_t* eligibility(const uint8_t* allow, int64_t mask_key);
   // scan dtype: SR_DTYPE_F16 (default) or SR_DTYPE_FP8_E4M3 (fp8 copy + exact fp16 re-scoring)

@@ -448,6 +448,47 @@ void Store::search_host(const float* q, int B, int k, float* out_dist, int64_t* 
     out_dist[i] = out_rows[i] >= 0 ? 1.0f - out_dist[i] : INFINITY;
 }
 
+void Store::mmr_dev(const int64_t* cand_rows, const float* cand_sims, int B, int K,
+                    int64_t row_offset, float lambda, int mode, float min_score, int k_out,
+                    float* out_score, float* out_sim, int64_t* out_rows, hipStream_t s) {
+  mmr_check_args(B, K, k_out, lambda, mode);
+  if (B == 0) return;
+  DeviceGuard g(device_);
+  begin(s);
+  launch_mmr_rerank(corpus_.as<half_t>(), ld_, n_rows_, cand_rows, row_offset, nullptr, cand_sims,
+                    nullptr, B, K, lambda, mode, min_score, k_out, out_score, out_sim, nullptr,
+                    out_rows, s);
+  end(s);
+}
+
+void Store::search_mmr_host(const float* q, int B, int k, int k_cand, float lambda, int mode,
+                            float min_score, const uint8_t* allow, int64_t mask_key,
+                            float* out_score, float* out_dist, int64_t* out_rows) {
+  mmr_check_args(B, k_cand, k, lambda, mode);
+  SR_CHECK(B == 0 || (q && out_score && out_dist && out_rows), "store.search_mmr: null buffer");
+  if (B == 0) return;
+  DeviceGuard g(device_);
+  const uint8_t* elig = eligibility(allow, mask_key);
+  // staging: queries | candidate rows | kept rows | candidate sims | kept score | kept sim
+  const size_t qb = (size_t)round_up((int64_t)B * dim_ * sizeof(float), 16);
+  const size_t nc = (size_t)B * k_cand, nk = (size_t)B * k;
+  qstage_.reserve(qb + nc * 12 + nk * 16);
+  float* dq = qstage_.as<float>();
+  int64_t* crows = reinterpret_cast<int64_t*>(qstage_.as<char>() + qb);
+  int64_t* drows = crows + nc;
+  float* csim = reinterpret_cast<float*>(drows + nk);
+  float* dscore = csim + nc;
+  float* dsim = dscore + nk;
+  SR_HIP(hipMemcpyAsync(dq, q, (size_t)B * dim_ * sizeof(float), hipMemcpyHostToDevice, stream_));
+  search_dev(dq, SR_DTYPE_F32, B, k_cand, csim, crows, 0, stream_, elig);
+  mmr_dev(crows, csim, B, k_cand, 0, lambda, mode, min_score, k, dscore, dsim, drows, stream_);
+  SR_HIP(hipMemcpyAsync(out_score, dscore, nk * sizeof(float), hipMemcpyDeviceToHost, stream_));
+  SR_HIP(hipMemcpyAsync(out_dist, dsim, nk * sizeof(float), hipMemcpyDeviceToHost, stream_));
+  SR_HIP(hipMemcpyAsync(out_rows, drows, nk * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
+  SR_HIP(hipStreamSynchronize(stream_));
+  for (size_t i = 0; i < nk; ++i) out_dist[i] = out_rows[i] >= 0 ? 1.0f - out_dist[i] : INFINITY;
+}
+
 // Snapshot format (little endian): "SRMISTO1", int32 dim, int64 n_rows, n_rows x dim fp16
 // (normalised rows, unpadded), n_rows bytes of live flags.  Written to "<path>.tmp", fsync'd and
 // renamed over <path>, so a crash mid-save leaves the previous snapshot intact.

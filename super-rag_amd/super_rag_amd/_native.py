@@ -28,6 +28,9 @@ SR_DTYPE_FP8_E4M3 = 2
 SR_POOL_CLS = 0
 SR_POOL_MEAN = 1
 SR_MAX_TOPK = 1024
+SR_MMR_ONEPASS = 0
+SR_MMR_GREEDY = 1
+SR_MMR_MAX_CAND = 128
 
 
 class NativeUnavailableError(RuntimeError):
@@ -79,6 +82,12 @@ SIGNATURES = {
                                     c_void_p]),
     "sr_store_search_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                     c_int64, c_void_p]),
+    "sr_mmr_rerank": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int,
+                              c_float, c_int, c_void_p, c_void_p, c_int]),
+    "sr_store_mmr_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_float, c_int,
+                                 c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sr_store_search_mmr": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_float,
+                                    c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "sr_store_set_scan_dtype": (c_int, [c_void_p, c_int]),
     "sr_store_save": (c_int, [c_void_p, c_char_p]),
     "sr_store_load": (c_int, [c_char_p, c_int, POINTER(c_void_p)]),

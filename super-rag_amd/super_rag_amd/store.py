@@ -163,6 +163,90 @@ class NativeStore:
         return out_sim, out_rows
 
 
+    def search_mmr(self, queries, k: int, fetch_k: int, lam: float = 0.5, mode: str = "onepass",
+                   min_score: float = -2.0, allow=None, mask_key: int = 0):
+        """Top-``fetch_k`` scan, then MMR diversification on the device, keep ``k``
+        (sr_store_search_mmr).  Returns (score [B,k] fp32 MMR score, -inf when missing; dist [B,k]
+        fp32 = 1 - cos of the kept rows, +inf when missing; rows [B,k] int64, -1 when missing), each
+        query's results in MMR order.  ``mode``: "onepass" (graphiti's function) or "greedy"."""
+        q = np.ascontiguousarray(np.asarray(queries, dtype=np.float32))
+        if q.ndim == 1:
+            q = q[None]
+        if q.shape[1] != self.dim:
+            raise ValueError(f"query dim {q.shape[1]} != store dim {self.dim}")
+        B = q.shape[0]
+        score = np.empty((B, k), dtype=np.float32)
+        dist = np.empty((B, k), dtype=np.float32)
+        rows = np.empty((B, k), dtype=np.int64)
+        a = None
+        if allow is not None:
+            n, _ = self.count()
+            a = np.ascontiguousarray(np.asarray(allow, dtype=np.uint8))
+            if a.shape != (n,):
+                raise ValueError(f"allow mask must have {n} entries, got {a.shape}")
+            if n == 0:
+                a = np.zeros(1, dtype=np.uint8)
+        N.call("sr_store_search_mmr", self._h, N.ptr(q), B, int(k), int(fetch_k), float(lam),
+               mmr_mode(mode), float(min_score), N.ptr(a) if a is not None else None,
+               int(mask_key) if a is not None else 0, N.ptr(score), N.ptr(dist), N.ptr(rows))
+        return score, dist, rows
+
+    def mmr_dev(self, cand_rows, cand_sims, k: int, lam: float = 0.5, mode: str = "onepass",
+                min_score: float = -2.0, row_offset: int = 0, stream=None):
+        """MMR over candidates as search_dev wrote them (device tensors [B, K]: rows carrying
+        ``row_offset``, -1 = missing; similarities).  Returns device tensors (score [B,k] fp32,
+        sim [B,k] fp32, rows [B,k] int64), -inf / -inf / -1 past the end (sr_store_mmr_dev)."""
+        import torch
+        assert cand_rows.is_cuda and cand_rows.is_contiguous() and cand_rows.dtype == torch.int64
+        assert cand_sims.is_cuda and cand_sims.is_contiguous() and cand_sims.dtype == torch.float32
+        assert cand_rows.shape == cand_sims.shape and cand_rows.dim() == 2
+        B, K = cand_rows.shape
+        out_score = torch.empty((B, k), dtype=torch.float32, device=cand_rows.device)
+        out_sim = torch.empty((B, k), dtype=torch.float32, device=cand_rows.device)
+        out_rows = torch.empty((B, k), dtype=torch.int64, device=cand_rows.device)
+        N.call("sr_store_mmr_dev", self._h, N.ptr(cand_rows), N.ptr(cand_sims), B, K, int(row_offset),
+               float(lam), mmr_mode(mode), float(min_score), int(k), N.ptr(out_score),
+               N.ptr(out_sim), N.ptr(out_rows), N.stream_handle(stream))
+        return out_score, out_sim, out_rows
+
+
+def mmr_mode(mode) -> int:
+    """"onepass" / "greedy" (or the SR_MMR_* code) -> SR_MMR_* code."""
+    if isinstance(mode, str):
+        try:
+            return {"onepass": N.SR_MMR_ONEPASS, "greedy": N.SR_MMR_GREEDY}[mode]
+        except KeyError:
+            raise ValueError(f"mmr mode must be 'onepass' or 'greedy', got {mode!r}") from None
+    return int(mode)
+
+
+def mmr_rerank(q, cand, n_cand=None, lam: float = 0.5, mode: str = "onepass",
+               min_score: float = -2.0, k: int | None = None, device: int = 0):
+    """MMR over explicit vectors (graphiti's maximal_marginal_relevance signature, batched):
+    q [B, dim], cand [B, K, dim] (host), ``n_cand`` [B] valid candidates per query (None: K).
+    Returns (score [B,k] fp32, index [B,k] int32 positions into the candidate list), -inf / -1
+    past the end; k defaults to K.  The query is normalised like the candidates
+    (sr_mmr_rerank)."""
+    qq = np.ascontiguousarray(np.asarray(q, dtype=np.float32))
+    c = np.ascontiguousarray(np.asarray(cand, dtype=np.float32))
+    if qq.ndim == 1:
+        qq, c = qq[None], (c[None] if c.ndim == 2 else c)
+    if c.ndim != 3 or c.shape[0] != qq.shape[0] or c.shape[2] != qq.shape[1]:
+        raise ValueError(f"expected q (B, dim) and cand (B, K, dim), got {qq.shape} and {c.shape}")
+    B, K, dim = c.shape
+    k = K if k is None else int(k)
+    nc = None
+    if n_cand is not None:
+        nc = np.ascontiguousarray(np.asarray(n_cand, dtype=np.int32))
+        if nc.shape != (B,) or (nc < 0).any() or (nc > K).any():
+            raise ValueError(f"n_cand must hold {B} counts in [0, {K}]")
+    score = np.empty((B, max(k, 0)), dtype=np.float32)
+    index = np.empty((B, max(k, 0)), dtype=np.int32)
+    N.call("sr_mmr_rerank", N.ptr(qq), N.ptr(c), N.ptr(nc) if nc is not None else None, B, K, dim,
+           float(lam), mmr_mode(mode), float(min_score), k, N.ptr(score), N.ptr(index), int(device))
+    return score, index
+
+
 def topk_merge_dev(sims, rows, k_out: int, device: int = 0, stream=None):
     """Merge [P, B, k] per-shard lists (device tensors) into [B, k_out] (sim desc, row asc)."""
     import torch
@@ -364,6 +448,34 @@ class ShardedStore:
         if allow is None and all(hasattr(sh, "search_dev") for sh in self.shards):
             return self._search_device(q, int(k))
         return self._search_host(q, int(k), allow, mask_key)
+
+    def search_mmr(self, queries, k: int, fetch_k: int, lam: float = 0.5, mode: str = "onepass",
+                   min_score: float = -2.0, allow=None, mask_key: int = 0):
+        """NativeStore.search_mmr over the shards: the merged top-``fetch_k`` of search(), those
+        rows read back with get() (stored rows re-normalise to themselves within fp16 rounding)
+        and diversified by mmr_rerank on the first device.  Returns (score, dist, rows)."""
+        q = np.ascontiguousarray(np.asarray(queries, dtype=np.float32))
+        if q.ndim == 1:
+            q = q[None]
+        k, fetch_k = int(k), int(fetch_k)
+        if not 1 <= k <= fetch_k <= N.SR_MMR_MAX_CAND:
+            raise ValueError(f"search_mmr needs 1 <= k <= fetch_k <= {N.SR_MMR_MAX_CAND}, "
+                             f"got k={k}, fetch_k={fetch_k}")
+        dist, rows = self.search(q, fetch_k, allow=allow, mask_key=mask_key)
+        B = q.shape[0]
+        ok = rows >= 0
+        n_cand = ok.sum(axis=1).astype(np.int32)          # the valid rows are a prefix
+        cand = np.zeros((B, fetch_k, self.dim), dtype=np.float32)
+        if ok.any():
+            cand[ok] = self.get(rows[ok])
+        score, index = mmr_rerank(q, cand, n_cand, lam=lam, mode=mode, min_score=min_score, k=k,
+                                  device=self.devices[0])
+        kept = index >= 0
+        pos = np.clip(index, 0, None).astype(np.int64)
+        out_rows = np.where(kept, np.take_along_axis(rows, pos, axis=1), -1)
+        out_dist = np.where(kept, np.take_along_axis(np.asarray(dist, np.float32), pos, axis=1),
+                            np.float32(np.inf)).astype(np.float32)
+        return score, out_dist, out_rows
 
     def _search_host(self, q, k, allow, mask_key):
         B = q.shape[0]

@@ -15,6 +15,10 @@ reference's ``fulltext_search`` node type, and ctx ``hybrid`` makes ``search`` f
 the BM25 rankings by reciprocal rank on the device (score = rrf score, descending).  Both work on
 collections sharded over several devices (ctx ``devices``: lexical.ShardedLex, corpus-wide BM25
 statistics), with the same results as one device.
+Opt-in diversification (ctx ``diversify="mmr"``, ``mmr_lambda``, ``mmr_mode``, ``mmr_fetch_k``, each
+overridable per call by a kwarg of the same name): ``search`` scans the top ``mmr_fetch_k`` rows and
+keeps ``top_k`` of them by maximal marginal relevance on the device (k_mmr.hip); results come in MMR
+order and ``score`` stays the cosine distance.
 Collections are process-wide (like a server): every connector object for the same collection
 name sees the same rows.  Row ids <-> uuid strings, texts and metadata live on the host; vectors
 live in HBM.  With ``ctx["snapshot_dir"]`` a collection is reloaded at construction and
@@ -280,6 +284,16 @@ class MI355XVectorStoreConnector:
         self.hybrid_k_each = ctx.get("hybrid_k_each")
         self.rrf_rank_const = int(ctx.get("rrf_rank_const", 1))
         self.scan_dtype = str(ctx.get("scan_dtype", "fp16"))   # "fp8": e4m3 scan + fp16 re-score
+        # opt-in diversification: MMR over the top mmr_fetch_k rows on the device (k_mmr.hip);
+        # each key can be overridden per call by a search kwarg of the same name
+        self.diversify = ctx.get("diversify")
+        if self.diversify not in (None, "mmr"):
+            raise ValueError(f"unsupported diversify '{self.diversify}' (None or 'mmr')")
+        self.mmr_lambda = float(ctx.get("mmr_lambda", 0.5))      # graphiti DEFAULT_MMR_LAMBDA
+        self.mmr_mode = str(ctx.get("mmr_mode", "onepass"))
+        self.mmr_fetch_k = ctx.get("mmr_fetch_k")                # None: min(128, max(4 top_k, 20))
+        if self.hybrid and self.diversify:
+            raise ValueError("hybrid and diversify cannot be combined (rrf scores are not cosines)")
         self.checkpoint_ratio = float(ctx.get("checkpoint_ratio", 1.0))
         self.store = self
         if self.snapshot_dir and _get(self.collection_name) is None:
@@ -397,6 +411,37 @@ class MI355XVectorStoreConnector:
         c.row_of = {u: i for i, u in enumerate(c.ids)}
 
     # -- query ------------------------------------------------------------------------------------
+    def _mmr_params(self, kwargs, top_k: int):
+        """None (diversify off: the search item stays the (q, k, filter) it is today) or the
+        (lambda, mode, fetch_k) of this call: ctx keys, each overridden by a kwarg of its name."""
+        div = kwargs.get("diversify", self.diversify)
+        if div is None:
+            return None
+        if div != "mmr":
+            raise ValueError(f"unsupported diversify '{div}' (None or 'mmr')")
+        if self.hybrid:
+            raise ValueError("hybrid and diversify cannot be combined (rrf scores are not cosines)")
+        from ._native import SR_MMR_MAX_CAND as cap
+        lam = float(kwargs.get("mmr_lambda", self.mmr_lambda))
+        mode = str(kwargs.get("mmr_mode", self.mmr_mode))
+        if mode not in ("onepass", "greedy"):
+            raise ValueError(f"mmr_mode must be 'onepass' or 'greedy', got {mode!r}")
+        if not 0.0 <= lam <= 1.0:
+            raise ValueError(f"mmr_lambda must be in [0, 1], got {lam}")
+        fetch = kwargs.get("mmr_fetch_k", self.mmr_fetch_k)
+        if int(top_k) > cap:
+            raise ValueError(f"diversify='mmr': top_k {int(top_k)} exceeds the cap of {cap} candidates")
+        if fetch is None:
+            fetch = min(cap, max(4 * int(top_k), 20))
+        elif int(fetch) > cap:
+            raise ValueError(f"diversify='mmr': mmr_fetch_k {int(fetch)} exceeds the cap of {cap} "
+                             f"candidates")
+        return lam, mode, max(int(fetch), int(top_k))
+
+    @staticmethod
+    def _item(q, k: int, flt, mmr):
+        return (q, k, flt) if mmr is None else (q, k, flt, mmr)
+
     def search(self, query, **kwargs):
         c = _get(self.collection_name)
         if c is None or query.top_k is None or query.top_k <= 0:
@@ -404,15 +449,16 @@ class MI355XVectorStoreConnector:
         q = np.asarray(query.embedding, dtype=np.float32)
         flt = kwargs.get("filter") if self.honor_filter else None
         thr = kwargs.get("score_threshold") if self.honor_score_threshold else None
+        mmr = self._mmr_params(kwargs, query.top_k)
         if self.hybrid:
             # rrf of the dense and the BM25 rankings on the device; score = rrf score (desc)
             return QueryResult(query=query.query,
                                results=self._hybrid(c, q, query.query or "", int(query.top_k), flt))
         if self.coalesce:
             # concurrent single-query searches share one device batch (coalesce.py)
-            results = self._coalescer(c)((q, int(query.top_k), flt))
+            results = self._coalescer(c)(self._item(q, int(query.top_k), flt, mmr))
         else:
-            results = self._search_batch(c, [(q, int(query.top_k), flt)])[0]
+            results = self._search_batch(c, [self._item(q, int(query.top_k), flt, mmr)])[0]
         return QueryResult(query=query.query, results=self._threshold(results, thr))
 
     async def asearch(self, query, **kwargs):
@@ -425,7 +471,8 @@ class MI355XVectorStoreConnector:
         q = np.asarray(query.embedding, dtype=np.float32)
         flt = kwargs.get("filter") if self.honor_filter else None
         thr = kwargs.get("score_threshold") if self.honor_score_threshold else None
-        results = await self._coalescer(c).acall((q, int(query.top_k), flt))
+        mmr = self._mmr_params(kwargs, query.top_k)
+        results = await self._coalescer(c).acall(self._item(q, int(query.top_k), flt, mmr))
         return QueryResult(query=query.query, results=self._threshold(results, thr))
 
     def can_fuse_embed(self, embedding_model) -> bool:
@@ -459,7 +506,7 @@ class MI355XVectorStoreConnector:
             return QueryResult(query=text, results=[])
         flt = kwargs.get("filter") if self.honor_filter else None
         thr = kwargs.get("score_threshold") if self.honor_score_threshold else None
-        item = (text.replace("\n", " "), int(top_k), flt)
+        item = self._item(text.replace("\n", " "), int(top_k), flt, self._mmr_params(kwargs, top_k))
         results = await self._text_coalescer(c, embedding_model).acall(item)
         return QueryResult(query=text, results=self._threshold(results, thr))
 
@@ -475,8 +522,8 @@ class MI355XVectorStoreConnector:
                     embed_with = type(em)._embed_with
 
                     def run(items, c=c):
-                        vecs = embed_with(enc, tok, dev_b, [t for t, _, _ in items])
-                        return self._search_batch(c, [(vecs[i], k, flt) for i, (_, k, flt) in enumerate(items)])
+                        vecs = embed_with(enc, tok, dev_b, [it[0] for it in items])
+                        return self._search_batch(c, [(vecs[i],) + tuple(it[1:]) for i, it in enumerate(items)])
                     co = Coalescer(run, max_batch=min(self.max_batch, dev_b))
                     c.text_coalescers[key] = co
         return co
@@ -494,7 +541,8 @@ class MI355XVectorStoreConnector:
     def _threshold(results, thr):
         if thr is None:
             return results
-        # similarity = 1 - distance >= threshold (results are distance-ascending: a prefix)
+        # similarity = 1 - distance >= threshold (a filter, not a prefix cut: diversified results
+        # come in MMR order, not by distance)
         return [d for d in results if 1.0 - d.score >= float(thr)]
 
     @staticmethod
@@ -522,22 +570,31 @@ class MI355XVectorStoreConnector:
 
     @staticmethod
     def _search_batch(c: _Collection, items) -> List[List[DocumentWithScore]]:
-        """[(query vector, top_k, filter)] -> per query [DocumentWithScore] (distance asc, no
-        ids).  Queries with the same filter share one device search."""
+        """[(query vector, top_k, filter[, (mmr lambda, mode, fetch_k)])] -> per query
+        [DocumentWithScore] (distance asc, or MMR order for a diversified item; no ids).  Queries
+        with the same filter and the same MMR settings share one device search."""
         out: List[List[DocumentWithScore]] = [[] for _ in items]
-        groups: Dict[str, list] = {}
-        for i, (_, _, flt) in enumerate(items):
-            groups.setdefault("" if flt is None else json.dumps(flt, sort_keys=True, default=str),
-                              []).append(i)
+        groups: Dict[tuple, list] = {}
+        for i, it in enumerate(items):
+            flt = it[2]
+            fkey = "" if flt is None else json.dumps(flt, sort_keys=True, default=str)
+            groups.setdefault((fkey, it[3] if len(it) > 3 else None), []).append(i)
         with c.lock:
-            for key, idx in groups.items():
+            for (key, mmr), idx in groups.items():
                 Q = np.stack([np.asarray(items[i][0], dtype=np.float32).reshape(-1) for i in idx])
                 kmax = max(items[i][1] for i in idx)
-                if key == "":
+                allow, mkey = None, 0
+                if key != "":
+                    mkey, allow = MI355XVectorStoreConnector._allow_mask(c, items[idx[0]][2])
+                if mmr is not None:
+                    lam, mode, fetch_k = mmr
+                    with devices_gate(_store_devices(c.store), "search"):
+                        _, dist, rows = c.store.search_mmr(Q, kmax, fetch_k, lam=lam, mode=mode,
+                                                           allow=allow, mask_key=mkey)
+                elif key == "":
                     with devices_gate(_store_devices(c.store), "search"):
                         dist, rows = c.store.search(Q, kmax)
                 else:
-                    mkey, allow = MI355XVectorStoreConnector._allow_mask(c, items[idx[0]][2])
                     with devices_gate(_store_devices(c.store), "search"):
                         dist, rows = c.store.search(Q, kmax, allow=allow, mask_key=mkey)
                 for j, i in enumerate(idx):
