@@ -109,6 +109,21 @@ int sr_store_search_sim(sr_store* s, const float* q, int B, int k, const uint8_t
  * once at the end to check the candidate-overflow flag (and reruns the exact slow path if set). */
 int sr_store_search_dev(sr_store* s, const void* q, int q_dtype, int B, int k, float* out_sim,
                         int64_t* out_rows, int64_t row_offset, void* stream);
+/* Each query searches only the rows of its own list (pre-filtered search: the chat_id / indexer
+ * filters of context/context.py:74-111 resolved to row lists by the caller).  lists: CSR
+ * (list_off[n_lists + 1], list_off[0] == 0; list_rows strictly ascending inside a list, every row in
+ * [0, n_rows)); q_list[b] in [0, n_lists) names query b's list (lists may be shared and may be
+ * empty).  Tombstoned rows in a list are skipped.  out_sim / out_rows: B x k host buffers,
+ * (sim desc, row asc); -inf / -1 past the eligible rows.  Reads the fp16 rows in either scan mode.
+ * k obeys sr_store_search's limits; B == 0 is a no-op.  Anything else is SR_ERR_INVALID before any
+ * device work.  Blocking.  One launch scores every (query, row of its list) pair, whatever the
+ * number of distinct lists (k_subset.hip), where sr_store_search_masked scans the whole store once
+ * per mask.  Not provided: a device-pointer (*_dev) variant and an sr_store_set_* counterpart (a
+ * caller with several stores splits the lists per store and merges, as the Python ShardedStore
+ * does). */
+int sr_store_search_subset(sr_store* s, const float* q, int B, int k, const int32_t* q_list,
+                           int n_lists, const int64_t* list_off, const int64_t* list_rows,
+                           float* out_sim, int64_t* out_rows);
 /* Scan precision (BASELINE config 5 "fp8 MFMA GEMM path"): SR_DTYPE_F16 (default) or
  * SR_DTYPE_FP8_E4M3: an fp8 copy of the rows (per-row power-of-two scale) is scanned with the
  * block-scaled fp8 MFMA (half the HBM bytes of the fp16 scan), the top max(2k, k + 32) candidates

@@ -338,6 +338,16 @@ int sr_store_search_mmr(sr_store* s, const float* q, int B, int k, int k_cand, f
   SR_API_END
 }
 
+int sr_store_search_subset(sr_store* s, const float* q, int B, int k, const int32_t* q_list,
+                           int n_lists, const int64_t* list_off, const int64_t* list_rows,
+                           float* out_sim, int64_t* out_rows) {
+  SR_API_BEGIN
+  SR_NONNULL(s);
+  std::lock_guard<std::mutex> lk(s->impl->mu);
+  s->impl->search_subset_host(q, B, k, q_list, n_lists, list_off, list_rows, out_sim, out_rows);
+  SR_API_END
+}
+
 int sr_store_set_scan_dtype(sr_store* s, int dtype) {
   SR_API_BEGIN
   SR_NONNULL(s);

@@ -206,6 +206,25 @@ void launch_mmr_rerank(const half_t* rows, int64_t ld, int64_t n_rows, const int
                        int k_out, float* out_score, float* out_sim, int32_t* out_index,
                        int64_t* out_rows, hipStream_t s);
 
+// k_subset.hip — scores of per-query row lists as keys in the per-query candidate lists (K2
+// launch_topk_select finishes).  Lists: CSR list_off / list_rows (device).  Groups: grp_q [G][16]
+// query indices of the block (-1: none) that share list grp_list[g].  items [n_items][2] =
+// (group, first list position of a SR_SUBSET_CHUNK-row chunk, relative to pass0), ordered
+// [list][chunk][group].  A pass covers list positions [pass0, pass0 + pass_rows); position i's key
+// goes to slot head + (i - pass0) (zero key for a row outside [0, n_rows)).  launch_subset_prep
+// (before every pass; q_list [B] = list of each query of the block) sets cnt and, for pass0 > 0,
+// zeroes the slots between the kept winners and k.  query_rows / group_rows: rows of the pass
+// summed over queries / groups (profiling only).
+constexpr int SR_SUBSET_CHUNK = 512;
+void launch_subset_prep(const int32_t* q_list, const int64_t* list_off, int64_t pass0,
+                        int pass_rows, int B, int k, uint64_t* cand, int cap, int* cnt,
+                        hipStream_t s);
+void launch_subset_scan(const half_t* corpus, int ld, int64_t n_rows, const half_t* Q,
+                        const int32_t* items, int n_items, const int32_t* grp_q,
+                        const int32_t* grp_list, const int64_t* list_off, const int64_t* list_rows,
+                        int64_t pass0, int pass_rows, int head, uint64_t* cand, int cap,
+                        double query_rows, double group_rows, hipStream_t s);
+
 // k_lex.hip — reciprocal-rank fusion of two ranked row lists per query (-1 padded), fp64 scores.
 void launch_rrf_fuse(const int64_t* rows_a, int ka, const int64_t* rows_b, int kb, int B,
                      int rank_const, double min_score, int k_out, double* out_score,

@@ -95,6 +95,12 @@ class Store {
   void search_mmr_host(const float* q, int B, int k, int k_cand, float lambda, int mode,
                        float min_score, const uint8_t* allow, int64_t mask_key, float* out_score,
                        float* out_dist, int64_t* out_rows);
+  // every query b searches only the rows of list q_list[b] (CSR list_off / list_rows, host; local
+  // row ids strictly ascending inside a list; lists may be shared or empty); out_sim descending,
+  // -inf / -1 past the eligible rows; reads the fp16 rows in either scan mode (k_subset.hip)
+  void search_subset_host(const float* q, int B, int k, const int32_t* q_list, int n_lists,
+                          const int64_t* list_off, const int64_t* list_rows, float* out_sim,
+                          int64_t* out_rows);
   // device eligibility mask live & allow (cached per mask_key and store version); null for null
   const uint8_t* eligibility(const uint8_t* allow, int64_t mask_key);
   // scan dtype: SR_DTYPE_F16 (default) or SR_DTYPE_FP8_E4M3 (fp8 copy + exact fp16 re-scoring)
@@ -139,6 +145,8 @@ class Store {
   // filtered search: device eligibility mask (live & allow) and what it was built from
   DevBuf mask_;
   int64_t version_ = 0, mask_key_ = 0, mask_version_ = -1, mask_rows_ = -1;
+  // subset search: list offsets | list rows | query lists, groups and work items of one call
+  DevBuf subset_;
 };
 
 // One collection row-sharded over several devices (store_set.cpp; C-ABI sr_store_set_*).

@@ -9,6 +9,7 @@
 // A per-query candidate list holds at most select_capacity() keys; if any list overflows (an
 // adversarial row order), the whole block is re-run in "safe" mode with chunks of
 // capacity - k rows, which can never overflow.  Results are exact either way.
+#include <algorithm>
 #include <cstdlib>
 #include <fstream>
 
@@ -446,6 +447,151 @@ void Store::search_host(const float* q, int B, int k, float* out_dist, int64_t* 
   if (raw_sim) return;
   for (int64_t i = 0; i < (int64_t)B * k; ++i)
     out_dist[i] = out_rows[i] >= 0 ? 1.0f - out_dist[i] : INFINITY;
+}
+
+// Subset search: every query scores only the rows of its own list (k_subset.hip), then K2.  Per
+// block of kQueryBlock queries the host sorts the queries by list and cuts them into groups of at
+// most 16 that share a list; a list longer than cap - k rows takes several passes with a select
+// between them, the structure of search_block's safe mode (the winners stay at the head of the
+// candidate list).  Always on the fp16 rows, whatever the scan dtype.
+void Store::search_subset_host(const float* q, int B, int k, const int32_t* q_list, int n_lists,
+                               const int64_t* list_off, const int64_t* list_rows, float* out_sim,
+                               int64_t* out_rows) {
+  SR_CHECK(B >= 0, "store.search_subset: negative batch");
+  if (B == 0) return;
+  SR_CHECK(q && q_list && list_off && out_sim && out_rows, "store.search_subset: null buffer");
+  SR_CHECK(k >= 1 && k <= SR_MAX_TOPK, "store.search_subset: top_k must be in [1, 1024]");
+  const int cap = select_capacity();
+  SR_CHECK(k <= cap / 4, "store.search_subset: top_k too large");
+  SR_CHECK(n_lists >= 1, "store.search_subset: at least one list is required");
+  SR_CHECK(list_off[0] == 0, "store.search_subset: list_off[0] must be 0");
+  for (int l = 0; l < n_lists; ++l)
+    SR_CHECK(list_off[l + 1] >= list_off[l], "store.search_subset: list_off must not decrease");
+  const int64_t total = list_off[n_lists];
+  SR_CHECK(total == 0 || list_rows, "store.search_subset: null list_rows");
+  for (int l = 0; l < n_lists; ++l)
+    for (int64_t i = list_off[l]; i < list_off[l + 1]; ++i) {
+      SR_CHECK(list_rows[i] >= 0 && list_rows[i] < n_rows_,
+               "store.search_subset: list row out of range");
+      SR_CHECK(i == list_off[l] || list_rows[i] > list_rows[i - 1],
+               "store.search_subset: list rows must be strictly ascending");
+    }
+  for (int b = 0; b < B; ++b)
+    SR_CHECK(q_list[b] >= 0 && q_list[b] < n_lists, "store.search_subset: q_list out of range");
+
+  // plan (host): meta = q_list [B] | per block: grp_q [G][16], grp_list [G], per pass items [n][2]
+  struct Pass {
+    size_t items;
+    int n_items;
+    int64_t pass0;
+    double query_rows, group_rows;
+  };
+  struct Block {
+    size_t grp_q, grp_list;
+    std::vector<Pass> passes;
+  };
+  const int pass_rows = cap - k;
+  std::vector<int32_t> meta(q_list, q_list + B);
+  std::vector<Block> blocks;
+  for (int b0 = 0; b0 < B; b0 += kQueryBlock) {
+    const int bb = std::min(kQueryBlock, B - b0);
+    std::vector<int> order(bb);
+    for (int i = 0; i < bb; ++i) order[i] = i;
+    std::stable_sort(order.begin(), order.end(),
+                     [&](int a, int b) { return q_list[b0 + a] < q_list[b0 + b]; });
+    struct Run {
+      int first_grp, n_grp, n_q;
+      int64_t len;
+    };
+    std::vector<Run> runs;
+    std::vector<int32_t> gq, gl;
+    int64_t max_len = 0;
+    for (int i = 0; i < bb;) {
+      const int l = q_list[b0 + order[i]];
+      int j = i;
+      while (j < bb && q_list[b0 + order[j]] == l) ++j;
+      Run r{(int)gl.size(), (int)ceil_div(j - i, 16), j - i, list_off[l + 1] - list_off[l]};
+      for (int g = 0; g < r.n_grp; ++g) {
+        gl.push_back(l);
+        for (int e = 0; e < 16; ++e) {
+          const int at = i + 16 * g + e;
+          gq.push_back(at < j ? order[at] : -1);
+        }
+      }
+      runs.push_back(r);
+      max_len = std::max(max_len, r.len);
+      i = j;
+    }
+    Block blk;
+    blk.grp_q = meta.size();
+    meta.insert(meta.end(), gq.begin(), gq.end());
+    blk.grp_list = meta.size();
+    meta.insert(meta.end(), gl.begin(), gl.end());
+    const int n_pass = (int)std::max<int64_t>(1, ceil_div(max_len, pass_rows));
+    for (int p = 0; p < n_pass; ++p) {
+      Pass ps{meta.size(), 0, (int64_t)p * pass_rows, 0.0, 0.0};
+      for (const Run& r : runs) {
+        const int64_t n = std::min<int64_t>(r.len - ps.pass0, pass_rows);
+        if (n <= 0) continue;
+        ps.query_rows += (double)n * r.n_q;
+        ps.group_rows += (double)n * r.n_grp;
+        for (int64_t c0 = 0; c0 < n; c0 += SR_SUBSET_CHUNK)
+          for (int g = 0; g < r.n_grp; ++g) {
+            meta.push_back(r.first_grp + g);
+            meta.push_back((int32_t)c0);
+            ++ps.n_items;
+          }
+      }
+      blk.passes.push_back(ps);
+    }
+    blocks.push_back(std::move(blk));
+  }
+
+  DeviceGuard g(device_);
+  begin(stream_);
+  ensure_query_ws(B);
+  const size_t off_bytes = (size_t)(n_lists + 1) * sizeof(int64_t);
+  const size_t row_bytes = (size_t)total * sizeof(int64_t);
+  subset_.reserve(off_bytes + row_bytes + meta.size() * sizeof(int32_t));
+  int64_t* d_off = subset_.as<int64_t>();
+  int64_t* d_rows = d_off + (n_lists + 1);
+  int32_t* d_meta = reinterpret_cast<int32_t*>(d_rows + total);
+  SR_HIP(hipMemcpyAsync(d_off, list_off, off_bytes, hipMemcpyHostToDevice, stream_));
+  if (total > 0)
+    SR_HIP(hipMemcpyAsync(d_rows, list_rows, row_bytes, hipMemcpyHostToDevice, stream_));
+  SR_HIP(hipMemcpyAsync(d_meta, meta.data(), meta.size() * sizeof(int32_t), hipMemcpyHostToDevice,
+                        stream_));
+  const size_t qb = (size_t)B * dim_ * sizeof(float);
+  qstage_.reserve(qb + (size_t)B * k * (sizeof(float) + sizeof(int64_t)));
+  float* dq = qstage_.as<float>();
+  float* dsim = reinterpret_cast<float*>(qstage_.as<char>() + qb);
+  int64_t* drows = reinterpret_cast<int64_t*>(dsim + (size_t)B * k);
+  SR_HIP(hipMemcpyAsync(dq, q, qb, hipMemcpyHostToDevice, stream_));
+  half_t* qn = qbuf_.as<half_t>();
+  launch_normalize_rows(dq, SR_DTYPE_F32, B, dim_, qn, ld_, stream_);
+  SR_HIP(hipMemsetAsync(overflow_.p, 0, sizeof(int), stream_));
+  uint64_t* cand = cand_.as<uint64_t>();
+  int* cnt = cnt_.as<int>();
+  for (size_t bi = 0; bi < blocks.size(); ++bi) {
+    const int b0 = (int)bi * kQueryBlock;
+    const int bb = std::min(kQueryBlock, B - b0);
+    const Block& blk = blocks[bi];
+    for (size_t p = 0; p < blk.passes.size(); ++p) {
+      const Pass& ps = blk.passes[p];
+      launch_subset_prep(d_meta + b0, d_off, ps.pass0, pass_rows, bb, k, cand, cap, cnt, stream_);
+      launch_subset_scan(corpus_.as<half_t>(), ld_, n_rows_, qn + (int64_t)b0 * ld_,
+                         d_meta + ps.items, ps.n_items, d_meta + blk.grp_q, d_meta + blk.grp_list,
+                         d_off, d_rows, ps.pass0, pass_rows, p == 0 ? 0 : k, cand, cap,
+                         ps.query_rows, ps.group_rows, stream_);
+      launch_topk_select(cand, cnt, cap, tau_.as<float>(), bb, k, overflow_.as<int>(),
+                         p + 1 == blk.passes.size(), dsim + (int64_t)b0 * k,
+                         drows + (int64_t)b0 * k, 0, stream_, live_.as<uint8_t>());
+    }
+  }
+  SR_HIP(hipMemcpyAsync(out_sim, dsim, (size_t)B * k * sizeof(float), hipMemcpyDeviceToHost, stream_));
+  SR_HIP(hipMemcpyAsync(out_rows, drows, (size_t)B * k * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
+  end(stream_);
+  SR_HIP(hipStreamSynchronize(stream_));
 }
 
 void Store::mmr_dev(const int64_t* cand_rows, const float* cand_sims, int B, int K,

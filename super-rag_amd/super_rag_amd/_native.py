@@ -88,6 +88,8 @@ SIGNATURES = {
                                  c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "sr_store_search_mmr": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_float,
                                     c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "sr_store_search_subset": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p,
+                                       c_void_p, c_void_p, c_void_p]),
     "sr_store_set_scan_dtype": (c_int, [c_void_p, c_int]),
     "sr_store_save": (c_int, [c_void_p, c_char_p]),
     "sr_store_load": (c_int, [c_char_p, c_int, POINTER(c_void_p)]),

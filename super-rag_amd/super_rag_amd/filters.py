@@ -56,6 +56,94 @@ def _field(cond: Any, val: Any) -> bool:
     return True
 
 
+def indexable(v: Any) -> bool:
+    """Values a field index keeps: hashable scalars, for which a dict lookup is the ``==`` of
+    _field (1 == 1.0 == True share a key, as they compare equal).  NaN equals nothing, itself
+    included, so it is left to ``matches``."""
+    return isinstance(v, (str, int, float, bool)) and v == v
+
+
+def _conjuncts(flt: Any):
+    """The clauses ``matches`` ANDs together: a clause list, and / $and and the keys of one mapping,
+    flattened; every returned clause is a one-key mapping.  None: not a filter ``matches`` accepts
+    (left to it to report)."""
+    if isinstance(flt, (list, tuple)):
+        parts = [_conjuncts(c) for c in flt]
+    elif isinstance(flt, Mapping):
+        parts = []
+        for key, cond in flt.items():
+            if key in ("and", "$and"):
+                if not isinstance(cond, (list, tuple)):
+                    return None
+                parts.extend(_conjuncts(c) for c in cond)
+            else:
+                parts.append([{key: cond}])
+    else:
+        return None
+    if any(p is None for p in parts):
+        return None
+    return [c for p in parts for c in p]
+
+
+def _clause_values(clause: Mapping, index: Mapping):
+    """(values, exact) when the clause is ``field: scalar``, ``{"$eq": scalar}`` or
+    ``{"$in": [scalars]}`` on an indexed field: the clause holds only for rows in the union of those
+    values' posting lists, and for all of them when ``exact`` (no further operator in the clause)."""
+    (key, cond), = clause.items()
+    if key in ("or", "$or", "not", "$not") or key not in index:
+        return None
+    if not isinstance(cond, Mapping):
+        return ([cond], True) if indexable(cond) else None
+    if "$eq" in cond and indexable(cond["$eq"]):
+        return [cond["$eq"]], len(cond) == 1
+    arg = cond.get("$in")
+    if isinstance(arg, (list, tuple)) and all(indexable(v) for v in arg):
+        return list(arg), len(cond) == 1
+    return None
+
+
+def plan(flt: Any, index: Mapping):
+    """Resolve a filter through a field index ``{field: {value: ascending rows}}``.
+
+    Returns None when no conjunct of the filter is an equality / $in clause on an indexed field
+    (the filter then takes the mask path), else ``(rows, rest)``: ``rows`` (ascending int64) is
+    the shortest posting list, or union of an $in's lists, among those clauses, a superset of the
+    matching rows; ``rest`` is the list of conjuncts still to be checked with ``matches`` on those
+    rows only (empty: ``rows`` is the answer)."""
+    import numpy as np
+    clauses = _conjuncts(flt) if flt is not None else None
+    if not clauses:
+        return None
+    best = None
+    for i, cl in enumerate(clauses):
+        got = _clause_values(cl, index)
+        if got is None:
+            continue
+        values, exact = got
+        posting = index[next(iter(cl))]
+        parts, seen = [], set()
+        for v in values:
+            if v not in seen:           # (1 and 1.0 name one posting list)
+                seen.add(v)
+                p = posting.get(v)
+                if p is not None and len(p):
+                    parts.append(p)
+        size = sum(len(p) for p in parts)
+        if best is None or size < best[0]:
+            best = (size, i, parts, exact)
+    if best is None:
+        return None
+    _, i, parts, exact = best
+    if not parts:
+        rows = np.zeros(0, np.int64)
+    elif len(parts) == 1:
+        rows = np.array(parts[0], dtype=np.int64)
+    else:
+        rows = np.unique(np.concatenate([np.asarray(p, dtype=np.int64) for p in parts]))
+    rest = [c for j, c in enumerate(clauses) if j != i or not exact]
+    return rows, rest
+
+
 def matches(flt: Any, metadata: Mapping | None) -> bool:
     """Does a row's metadata satisfy the filter?  ``None`` matches everything."""
     if flt is None:

@@ -146,6 +146,37 @@ class NativeStore:
                int(mask_key) if a is not None else 0, N.ptr(sim), N.ptr(rows))
         return np.where(rows >= 0, sim, -np.inf).astype(np.float32), rows
 
+    def search_subset(self, queries, k: int, lists, q_list=None, sim: bool = False):
+        """Pre-filtered search: query b searches only the rows of ``lists[q_list[b]]``
+        (sr_store_search_subset; one device launch whatever the number of distinct lists).
+        ``lists``: a sequence of int64 row arrays, each strictly ascending; ``q_list`` [B] defaults to
+        arange(B), which needs one list per query.  Returns (dist [B,k] fp32 = 1 - sim, +inf when
+        missing; rows [B,k] int64, -1 when missing) exactly as search() reports them, or with
+        ``sim=True`` (sim [B,k] descending, -inf when missing; rows).  Tombstoned rows are skipped;
+        the fp16 rows are read in either scan mode."""
+        q = np.ascontiguousarray(np.asarray(queries, dtype=np.float32))
+        if q.ndim == 1:
+            q = q[None]
+        if q.shape[1] != self.dim:
+            raise ValueError(f"query dim {q.shape[1]} != store dim {self.dim}")
+        B = q.shape[0]
+        off, flat = pack_lists(lists)
+        if q_list is None:
+            if len(lists) != B:
+                raise ValueError(f"search_subset: {len(lists)} lists for {B} queries and no q_list")
+            ql = np.arange(B, dtype=np.int32)
+        else:
+            ql = np.ascontiguousarray(np.asarray(q_list, dtype=np.int32))
+            if ql.shape != (B,):
+                raise ValueError(f"q_list must have {B} entries, got {ql.shape}")
+        s = np.empty((B, k), dtype=np.float32)
+        rows = np.empty((B, k), dtype=np.int64)
+        N.call("sr_store_search_subset", self._h, N.ptr(q), B, int(k), N.ptr(ql), len(lists),
+               N.ptr(off), N.ptr(flat), N.ptr(s), N.ptr(rows))
+        if sim:
+            return np.where(rows >= 0, s, -np.inf).astype(np.float32), rows
+        return np.where(rows >= 0, np.float32(1.0) - s, np.float32(np.inf)).astype(np.float32), rows
+
     def search_dev(self, q, k: int, out_sim=None, out_rows=None, row_offset: int = 0, stream=None):
         """Device path: q [B, >=dim] fp16/fp32 device tensor (only the first `dim` columns are
         read when q is exactly [B, dim]; a padded fp16 [B, ld] query must be sliced by the caller).
@@ -208,6 +239,17 @@ class NativeStore:
                float(lam), mmr_mode(mode), float(min_score), int(k), N.ptr(out_score),
                N.ptr(out_sim), N.ptr(out_rows), N.stream_handle(stream))
         return out_score, out_sim, out_rows
+
+
+def pack_lists(lists):
+    """Row lists -> CSR (list_off [n + 1] int64, list_rows int64), the layout of
+    sr_store_search_subset."""
+    arrs = [np.asarray(l, dtype=np.int64).reshape(-1) for l in lists]
+    off = np.zeros(len(arrs) + 1, dtype=np.int64)
+    if arrs:
+        np.cumsum([a.size for a in arrs], out=off[1:])
+    flat = np.ascontiguousarray(np.concatenate(arrs)) if arrs and off[-1] else np.zeros(1, np.int64)
+    return off, flat
 
 
 def mmr_mode(mode) -> int:
@@ -477,6 +519,48 @@ class ShardedStore:
                             np.float32(np.inf)).astype(np.float32)
         return score, out_dist, out_rows
 
+    def search_subset(self, queries, k: int, lists, q_list=None, sim: bool = False):
+        """NativeStore.search_subset over the shards: every list is split by shard (local ids stay
+        ascending: a shard's table is appended in global order), each shard searches its parts and
+        the short lists merge on the host by (similarity desc, global row asc), so the result is
+        the single store's."""
+        q = np.ascontiguousarray(np.asarray(queries, dtype=np.float32))
+        if q.ndim == 1:
+            q = q[None]
+        if q.shape[1] != self.dim:
+            raise ValueError(f"query dim {q.shape[1]} != store dim {self.dim}")
+        B, k = q.shape[0], int(k)
+        arrs = [np.asarray(l, dtype=np.int64).reshape(-1) for l in lists]
+        n = len(self.shard_of)
+        for a in arrs:
+            if a.size and (a.min() < 0 or a.max() >= n):
+                raise ValueError(f"search_subset: list row outside [0, {n})")
+        dists, rows = [], []
+        for s, sh in enumerate(self.shards):
+            parts = [self.local_of[a[self.shard_of[a] == s]] for a in arrs]
+            sm, r = sh.search_subset(q, k, parts, q_list=q_list, sim=True)
+            g = np.where(r >= 0, self.tables[s][np.clip(r, 0, None)] if len(self.tables[s]) else -1, -1)
+            dists.append(np.where(g >= 0, -np.asarray(sm, np.float64), np.inf))
+            rows.append(g)
+        out_d, out_r = self._merge_host(dists, rows, B, k)
+        ok = out_r >= 0
+        s32 = (-out_d).astype(np.float32)
+        if sim:
+            return np.where(ok, s32, -np.inf).astype(np.float32), out_r
+        return np.where(ok, np.float32(1.0) - s32, np.inf).astype(np.float32), out_r
+
+    @staticmethod
+    def _merge_host(dists, rows, B, k):
+        """Per-shard (merge key asc, global row) lists -> the k best per query, ties by row."""
+        D, R = np.concatenate(dists, 1), np.concatenate(rows, 1)
+        out_d = np.full((B, k), np.inf, D.dtype)
+        out_r = np.full((B, k), -1, np.int64)
+        for b in range(B):
+            big = np.where(R[b] >= 0, R[b], np.iinfo(np.int64).max)
+            o = np.lexsort((big, D[b]))[:k]
+            out_d[b], out_r[b] = D[b][o], np.where(np.isfinite(D[b][o]), R[b][o], -1)
+        return out_d, out_r
+
     def _search_host(self, q, k, allow, mask_key):
         B = q.shape[0]
         dists, rows = [], []
@@ -494,13 +578,7 @@ class ShardedStore:
             g = np.where(r >= 0, self.tables[s][np.clip(r, 0, None)] if len(self.tables[s]) else -1, -1)
             dists.append(np.where(g >= 0, d, np.inf))
             rows.append(g)
-        D, R = np.concatenate(dists, 1), np.concatenate(rows, 1)
-        out_d = np.full((B, k), np.inf, D.dtype)
-        out_r = np.full((B, k), -1, np.int64)
-        for b in range(B):
-            big = np.where(R[b] >= 0, R[b], np.iinfo(np.int64).max)
-            o = np.lexsort((big, D[b]))[:k]
-            out_d[b], out_r[b] = D[b][o], np.where(np.isfinite(D[b][o]), R[b][o], -1)
+        out_d, out_r = self._merge_host(dists, rows, B, k)
         if exact:  # -sim -> 1 - sim in fp32, as the single store reports it
             ok = out_r >= 0
             out_d = np.where(ok, (np.float32(1.0) - (-out_d).astype(np.float32)), np.inf).astype(np.float32)

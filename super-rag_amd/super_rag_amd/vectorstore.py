@@ -19,6 +19,12 @@ Opt-in diversification (ctx ``diversify="mmr"``, ``mmr_lambda``, ``mmr_mode``, `
 overridable per call by a kwarg of the same name): ``search`` scans the top ``mmr_fetch_k`` rows and
 keeps ``top_k`` of them by maximal marginal relevance on the device (k_mmr.hip); results come in MMR
 order and ``score`` stays the cosine distance.
+Opt-in pre-filtering (ctx ``filter_index=[fields]`` with ``honor_filter``; ``subset_max_rows``): the
+collection keeps ``value -> rows`` posting lists of the named metadata fields; a filter with an
+equality / $in clause on such a field (filters.plan) is resolved to its row list on the host and
+ALL such items of a batch, whatever their filters, go to the device in one search_subset call that
+scores only those rows (k_subset.hip) instead of one masked full scan per distinct filter.  Same
+results; every other filter, diversified and hybrid / fulltext searches keep the mask path.
 Collections are process-wide (like a server): every connector object for the same collection
 name sees the same rows.  Row ids <-> uuid strings, texts and metadata live on the host; vectors
 live in HBM.  With ``ctx["snapshot_dir"]`` a collection is reloaded at construction and
@@ -28,6 +34,7 @@ from __future__ import annotations
 
 import asyncio
 
+from array import array
 import copy
 import json
 from collections import OrderedDict
@@ -46,6 +53,8 @@ logger = logging.getLogger(__name__)
 
 VECTOR_DB_TYPE = "mi355x"
 MASK_CACHE_SIZE = 8      # filter masks kept per collection (n_rows bytes each)
+SUBSET_MAX_ROWS = 65536  # ctx "subset_max_rows": longest resolved list the subset path takes
+SUBSET_CACHE_ROWS = 1 << 22   # resolved row lists kept per collection, by total rows (8 bytes each)
 
 
 def _native_store(dim: int, device: int):
@@ -143,6 +152,55 @@ class _Collection:
         self.lex = None         # BM25 index over the same rows (ctx "fulltext"), lexical.py
         self.vocab = None
         self.journal = None     # persist.Journal with ctx["snapshot_dir"]
+        # ctx "filter_index": field -> {value: array('q') of ascending rows} (hashable scalar values
+        # only; tombstoned rows stay listed, the device drops them), None until a connector asks
+        self.findex: Optional[Dict[str, Dict[Any, array]]] = None
+        self.subset_max_rows = SUBSET_MAX_ROWS
+        # filter -> (version, resolved rows or None when the list is too long, the subset_max_rows
+        # that decided it): LRU bounded by total rows
+        self.subsets: "OrderedDict[str, tuple]" = OrderedDict()
+
+    def ensure_index(self, fields) -> None:
+        """Index the named metadata fields, back-filling the rows added before."""
+        new = [f for f in fields if self.findex is None or f not in self.findex]
+        if not new:
+            return
+        if self.findex is None:
+            self.findex = {}
+        for f in new:
+            self.findex[f] = {}
+        self.index_rows(0, self.metadatas, new)
+
+    def index_rows(self, first: int, metadatas, fields=None) -> None:
+        """Append rows first .. first + len(metadatas) - 1 to the posting lists."""
+        if self.findex is None:
+            return
+        from .filters import indexable
+        for f in (self.findex if fields is None else fields):
+            posting = self.findex[f]
+            for r, md in enumerate(metadatas, first):
+                if md:
+                    v = md.get(f)
+                    if v is not None and indexable(v):
+                        p = posting.get(v)
+                        if p is None:
+                            p = posting[v] = array("q")
+                        p.append(r)
+
+    def remap_index(self, remap) -> None:
+        """Renumber the posting lists through a compaction's old -> new row map (-1: dropped)."""
+        if self.findex is None:
+            return
+        remap = np.asarray(remap, dtype=np.int64)
+        for f, posting in self.findex.items():
+            out = {}
+            for v, p in posting.items():
+                new = remap[np.frombuffer(p, dtype=np.int64)] if len(p) else np.zeros(0, np.int64)
+                new = new[new >= 0]
+                if new.size:
+                    out[v] = array("q", new.tolist())
+            self.findex[f] = out
+        self.subsets.clear()
 
     def ensure_lex(self) -> None:
         """Create the lexical index, back-filling the rows added before it existed.  A collection
@@ -195,6 +253,7 @@ class _Collection:
             if self.lex is not None:
                 from .lexical import analyze
                 self.lex.add([self.vocab.doc_ids(analyze(t)) for t in rec["texts"]])
+            self.index_rows(len(self.ids), rec["metadatas"])
             for u, t, m in zip(rec["ids"], rec["texts"], rec["metadatas"]):
                 self.row_of[u] = len(self.ids)
                 self.ids.append(u)
@@ -294,6 +353,13 @@ class MI355XVectorStoreConnector:
         self.mmr_fetch_k = ctx.get("mmr_fetch_k")                # None: min(128, max(4 top_k, 20))
         if self.hybrid and self.diversify:
             raise ValueError("hybrid and diversify cannot be combined (rrf scores are not cosines)")
+        # opt-in pre-filtering: posting lists of these metadata fields; a filter they resolve
+        # searches only its rows (one search_subset call per batch).  Needs honor_filter.
+        fi = ctx.get("filter_index")
+        if isinstance(fi, str):
+            fi = [fi]
+        self.filter_index = [str(f) for f in fi] if fi and self.honor_filter else None
+        self.subset_max_rows = int(ctx.get("subset_max_rows", SUBSET_MAX_ROWS))
         self.checkpoint_ratio = float(ctx.get("checkpoint_ratio", 1.0))
         self.store = self
         if self.snapshot_dir and _get(self.collection_name) is None:
@@ -305,6 +371,13 @@ class MI355XVectorStoreConnector:
         c = _get(self.collection_name)
         if c is not None:
             self._apply_scan_dtype(c)
+            self._apply_filter_index(c)
+
+    def _apply_filter_index(self, c: _Collection) -> None:
+        if self.filter_index:
+            with c.lock:
+                c.ensure_index(self.filter_index)
+                c.subset_max_rows = self.subset_max_rows
 
     def _apply_scan_dtype(self, c: _Collection) -> None:
         if getattr(c, "scan_dtype", "fp16") != self.scan_dtype and hasattr(c.store, "set_scan_dtype"):
@@ -324,6 +397,7 @@ class MI355XVectorStoreConnector:
                     c.journal = Journal(self.snapshot_dir, self.collection_name)
                 _collections[self.collection_name] = c
         self._apply_scan_dtype(c)
+        self._apply_filter_index(c)
         return c
 
     def create_collection(self, **kwargs: Any):
@@ -368,6 +442,7 @@ class MI355XVectorStoreConnector:
                 c.row_of[u] = int(r)
                 c.texts.append(n.text)
                 c.metadatas.append(copy.deepcopy(n.metadata) if n.metadata is not None else None)
+            c.index_rows(first, c.metadatas[first:])
             c.version += 1
             c.persist_add(first, vecs, ids, c.texts[first:], c.metadatas[first:])
             c.maybe_checkpoint(self.checkpoint_ratio)
@@ -404,6 +479,7 @@ class MI355XVectorStoreConnector:
         if c.lex is not None:
             lremap = c.lex.compact()
             assert np.array_equal(np.asarray(lremap), np.asarray(remap)), "lexical remap differs"
+        c.remap_index(remap)
         keep = [i for i, r in enumerate(remap) if r >= 0]
         c.ids = [c.ids[i] for i in keep]
         c.texts = [c.texts[i] for i in keep]
@@ -569,17 +645,83 @@ class MI355XVectorStoreConnector:
         return mkey, allow
 
     @staticmethod
+    def _subset_rows(c: _Collection, flt):
+        """The ascending rows a filter resolves to through the field index (filters.plan, its
+        remaining clauses checked with ``matches`` on the posting list's rows only), or None when
+        the filter is not resolvable or its list exceeds subset_max_rows.  Cached per filter and
+        collection version; the cache is bounded by its total rows."""
+        from .filters import canonical, matches, plan
+        key = canonical(flt)
+        hit = c.subsets.get(key)
+        if hit is not None and hit[0] == c.version and hit[2] == c.subset_max_rows:
+            c.subsets.move_to_end(key)
+            return hit[1]
+        got = plan(flt, c.findex)
+        if got is None:
+            return None
+        rows, rest = got
+        if rest:
+            md = c.metadatas
+            rows = rows[np.fromiter((matches(rest, md[r]) for r in rows.tolist()), dtype=bool,
+                                    count=len(rows))]
+        if len(rows) > c.subset_max_rows:
+            rows = None
+        for k in [k for k, v in c.subsets.items() if v[0] != c.version]:
+            del c.subsets[k]                    # stale: the rows changed since
+        c.subsets[key] = (c.version, rows, c.subset_max_rows)
+        c.subsets.move_to_end(key)
+        total = sum(len(v[1]) for v in c.subsets.values() if v[1] is not None)
+        while total > SUBSET_CACHE_ROWS and len(c.subsets) > 1:
+            _, old = c.subsets.popitem(last=False)
+            total -= 0 if old[1] is None else len(old[1])
+        return rows
+
+    @staticmethod
+    def _has_subset(store) -> bool:
+        shards = getattr(store, "shards", None)
+        if shards is not None:
+            return all(hasattr(sh, "search_subset") for sh in shards)
+        return hasattr(store, "search_subset")
+
+    @staticmethod
     def _search_batch(c: _Collection, items) -> List[List[DocumentWithScore]]:
         """[(query vector, top_k, filter[, (mmr lambda, mode, fetch_k)])] -> per query
-        [DocumentWithScore] (distance asc, or MMR order for a diversified item; no ids).  Queries
-        with the same filter and the same MMR settings share one device search."""
+        [DocumentWithScore] (distance asc, or MMR order for a diversified item; no ids).  With a
+        field index, every undiversified item whose filter resolves to a row list goes to the store
+        in ONE search_subset call (items with the same filter share a list); the other queries
+        share one device search per filter and MMR setting."""
         out: List[List[DocumentWithScore]] = [[] for _ in items]
         groups: Dict[tuple, list] = {}
-        for i, it in enumerate(items):
-            flt = it[2]
-            fkey = "" if flt is None else json.dumps(flt, sort_keys=True, default=str)
-            groups.setdefault((fkey, it[3] if len(it) > 3 else None), []).append(i)
         with c.lock:
+            sub_idx, sub_list, lists, list_of = [], [], [], {}
+            use_subset = c.findex is not None and MI355XVectorStoreConnector._has_subset(c.store)
+            for i, it in enumerate(items):
+                flt = it[2]
+                fkey = "" if flt is None else json.dumps(flt, sort_keys=True, default=str)
+                mmr = it[3] if len(it) > 3 else None
+                if use_subset and flt is not None and mmr is None:
+                    li = list_of.get(fkey)
+                    if li is None:
+                        rows = MI355XVectorStoreConnector._subset_rows(c, flt)
+                        li = list_of[fkey] = -1 if rows is None else len(lists)
+                        if rows is not None:
+                            lists.append(rows)
+                    if li >= 0:
+                        sub_idx.append(i)
+                        sub_list.append(li)
+                        continue
+                groups.setdefault((fkey, mmr), []).append(i)
+            if sub_idx:
+                Q = np.stack([np.asarray(items[i][0], dtype=np.float32).reshape(-1) for i in sub_idx])
+                kmax = max(items[i][1] for i in sub_idx)
+                with devices_gate(_store_devices(c.store), "search"):
+                    dist, rows = c.store.search_subset(Q, kmax, lists,
+                                                       q_list=np.asarray(sub_list, dtype=np.int32))
+                for j, i in enumerate(sub_idx):
+                    k = items[i][1]
+                    out[i] = [_make_doc(text=c.texts[r], score=float(d),
+                                        metadata=_json_copy(c.metadatas[r]))
+                              for d, r in zip(dist[j, :k].tolist(), rows[j, :k].tolist()) if r >= 0]
             for (key, mmr), idx in groups.items():
                 Q = np.stack([np.asarray(items[i][0], dtype=np.float32).reshape(-1) for i in idx])
                 kmax = max(items[i][1] for i in idx)
