@@ -215,6 +215,49 @@ int sr_store_search_mmr(sr_store* s, const float* q, int B, int k, int k_cand,
                         int64_t* out_rows);
 
 /* ------------------------------------------------------------------------------------------------
+ * Grouped search (Qdrant search_groups, Milvus group_by_field): the k best DISTINCT groups of a
+ * query with the best row or rows of each, exact (k_group.hip).  The indexer stores every doc_part of
+ * a document_id as a row of its own, so the k nearest rows are often k chunks of one document.
+ * group: host int32 [n_rows]; g >= 0 names a group, -1 makes the row a group of its own, any other
+ * value is an error.  It is kept on the device and reused while group_key (non-zero) and the store
+ * contents are unchanged; group_key 0 uploads (and validates) it every call.
+ * Semantics: walk all eligible rows (live, and allowed when allow is given) in the store's order
+ * (similarity desc, row asc); a row is kept when its group holds fewer than group_size kept rows and
+ * its group is already kept or fewer than k groups are.  Groups come in order of first appearance
+ * (the order of their best rows), the rows of a group in walk order.  out_sim / out_rows:
+ * B x k x group_size, SIMILARITIES (not distances), -inf / -1 in unfilled slots; out_group: B x k, -1
+ * for an unfilled group slot (its first row is -1, which tells it from an ungrouped row's slot).
+ * Limits: k in [1, SR_MAX_TOPK], group_size in [1, SR_GROUP_MAX_SIZE], k * group_size <= k_cand <=
+ * SR_MAX_TOPK (and sr_store_search's limit on k applies to k_cand); B == 0 is a no-op; anything
+ * else, a null buffer or an id below -1 is SR_ERR_INVALID before any device work.
+ * Not provided: an sr_store_set_* counterpart (the Python ShardedStore merges per-shard results by
+ * the same walk) and grouped MMR / hybrid / subset search.
+ * ---------------------------------------------------------------------------------------------- */
+#define SR_GROUP_MAX_SIZE 8
+
+/* Blocking, exact.  Scans the top k_cand rows (sr_store_search_sim semantics, allow may be NULL) and
+ * collapses them on the device; a query whose k_cand rows do not settle the answer (a few large
+ * groups fill the list) continues on its own with the settled groups masked out, at most k more
+ * scans, so the result never depends on k_cand.  SR_ERR_STATE if that bound were ever exceeded.
+ * Under the fp8 scan mode the candidates carry their exact fp16 re-scored similarities. */
+int sr_store_search_grouped(sr_store* s, const float* q, int B, int k, int group_size, int k_cand,
+                            const int32_t* group, int64_t group_key,
+                            const uint8_t* allow, int64_t mask_key,
+                            float* out_sim, int64_t* out_rows, int32_t* out_group);
+
+/* Collapse a candidate list that sr_store_search_dev wrote (device buffers B x K: rows carrying
+ * row_offset, -1 = missing; similarities), k * group_size <= K <= SR_MAX_TOPK.  Device outputs as
+ * above (rows keep row_offset) plus out_complete [B] int32: 1 when query b's result is already
+ * exact (the list was not full, or k groups were found and each holds group_size rows or is an
+ * ungrouped row), 0 when only a continuation could tell.  No continuation here.  group is a HOST
+ * array, as above.  Asynchronous on stream. */
+int sr_store_group_dev(sr_store* s, const int64_t* cand_rows, const float* cand_sims, int B, int K,
+                       int64_t row_offset, int k, int group_size,
+                       const int32_t* group, int64_t group_key,
+                       float* out_sim, int64_t* out_rows, int32_t* out_group,
+                       int32_t* out_complete, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Lexical (BM25) index and hybrid dense + lexical retrieval  (BASELINE config 5)
  * The reference declares a `fulltext_search` node type (schema/view_models.py:276-283,
  * FulltextSearchParams{topk, keywords} at :1043-1047) and a merge slot for its output

@@ -348,6 +348,47 @@ int sr_store_search_subset(sr_store* s, const float* q, int B, int k, const int3
   SR_API_END
 }
 
+// ---- grouped search (k_group.hip) ----------------------------------------------------------------
+int sr_store_search_grouped(sr_store* s, const float* q, int B, int k, int group_size, int k_cand,
+                            const int32_t* group, int64_t group_key, const uint8_t* allow,
+                            int64_t mask_key, float* out_sim, int64_t* out_rows,
+                            int32_t* out_group) {
+  SR_API_BEGIN
+  SR_NONNULL(s);
+  sr::group_check_args(B, k_cand, k, group_size);
+  if (B == 0) return SR_OK;
+  SR_NONNULL(q);
+  SR_NONNULL(group);
+  SR_NONNULL(out_sim);
+  SR_NONNULL(out_rows);
+  SR_NONNULL(out_group);
+  std::lock_guard<std::mutex> lk(s->impl->mu);
+  s->impl->search_grouped_host(q, B, k, group_size, k_cand, group, group_key, allow,
+                               allow ? mask_key : 0, out_sim, out_rows, out_group);
+  SR_API_END
+}
+
+int sr_store_group_dev(sr_store* s, const int64_t* cand_rows, const float* cand_sims, int B, int K,
+                       int64_t row_offset, int k, int group_size, const int32_t* group,
+                       int64_t group_key, float* out_sim, int64_t* out_rows, int32_t* out_group,
+                       int32_t* out_complete, void* stream) {
+  SR_API_BEGIN
+  SR_NONNULL(s);
+  sr::group_check_args(B, K, k, group_size);
+  if (B == 0) return SR_OK;
+  SR_NONNULL(cand_rows);
+  SR_NONNULL(cand_sims);
+  SR_NONNULL(group);
+  SR_NONNULL(out_sim);
+  SR_NONNULL(out_rows);
+  SR_NONNULL(out_group);
+  SR_NONNULL(out_complete);
+  std::lock_guard<std::mutex> lk(s->impl->mu);
+  s->impl->group_dev(cand_rows, cand_sims, B, K, row_offset, k, group_size, group, group_key,
+                     out_sim, out_rows, out_group, out_complete, reinterpret_cast<hipStream_t>(stream));
+  SR_API_END
+}
+
 int sr_store_set_scan_dtype(sr_store* s, int dtype) {
   SR_API_BEGIN
   SR_NONNULL(s);

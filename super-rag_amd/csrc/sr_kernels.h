@@ -225,6 +225,27 @@ void launch_subset_scan(const half_t* corpus, int ld, int64_t n_rows, const half
                         int64_t pass0, int pass_rows, int head, uint64_t* cand, int cap,
                         double query_rows, double group_rows, hipStream_t s);
 
+// k_group.hip — grouped search: the k best distinct groups of a query with the group_size best rows
+// of each.  launch_group_collapse (one workgroup per query) walks the K candidates search_dev wrote
+// (cand_rows carry row_offset, -1 past the end) together with C rows carried from earlier rounds
+// (same form; C == 0: none); group [n_rows] int32: >= 0 a group, -1 a group of its own.  Outputs:
+// B x k x group_size similarity / row (-inf / -1 unfilled), B x k group id (-1), per query n_groups,
+// complete (the result is already exact) and found [B][k]: ascending (group key << 1 | full), the
+// state launch_group_mask reads; next_sims / next_rows (or null) receive the rows of the full
+// groups in the output layout, the next round's carried rows.  launch_group_mask (one query):
+// out[row] = base[row] && the row's group can still take rows (not full; not found counts only
+// while fewer than k groups are found).  group_check_args throws SR_ERR_INVALID outside the limits.
+void group_check_args(int B, int K, int k, int group_size);
+void launch_group_collapse(const float* cand_sims, const int64_t* cand_rows, int B, int K,
+                           const float* carry_sims, const int64_t* carry_rows, int C,
+                           int64_t row_offset, const int32_t* group, int64_t n_rows, int k,
+                           int group_size, float* out_sim, int64_t* out_rows, int32_t* out_group,
+                           int32_t* n_groups, int32_t* complete, uint64_t* found, float* next_sims,
+                           int64_t* next_rows, hipStream_t s);
+void launch_group_mask(const uint8_t* base, const int32_t* group, int64_t n_rows,
+                       const uint64_t* found, const int32_t* n_groups, int k, uint8_t* out,
+                       hipStream_t s);
+
 // k_lex.hip — reciprocal-rank fusion of two ranked row lists per query (-1 padded), fp64 scores.
 void launch_rrf_fuse(const int64_t* rows_a, int ka, const int64_t* rows_b, int kb, int B,
                      int rank_const, double min_score, int k_out, double* out_score,

@@ -101,6 +101,19 @@ class Store {
   void search_subset_host(const float* q, int B, int k, const int32_t* q_list, int n_lists,
                           const int64_t* list_off, const int64_t* list_rows, float* out_sim,
                           int64_t* out_rows);
+  // grouped search (k_group.hip): the k best distinct groups with the group_size best rows of each,
+  // exact: search_dev for the top k_cand, group_collapse, and continuation rounds for the queries
+  // whose list did not settle the answer.  group: host int32 [n_rows] (>= 0 a group, -1 a group of
+  // its own), cached on the device per group_key like the allow mask.  out_sim: similarities.
+  void search_grouped_host(const float* q, int B, int k, int group_size, int k_cand,
+                           const int32_t* group, int64_t group_key, const uint8_t* allow,
+                           int64_t mask_key, float* out_sim, int64_t* out_rows, int32_t* out_group);
+  // group_collapse over candidates as search_dev wrote them; no continuation; asynchronous on s
+  void group_dev(const int64_t* cand_rows, const float* cand_sims, int B, int K, int64_t row_offset,
+                 int k, int group_size, const int32_t* group, int64_t group_key, float* out_sim,
+                 int64_t* out_rows, int32_t* out_group, int32_t* out_complete, hipStream_t s);
+  // device copy of a host group array (validated; cached per group_key and store version)
+  const int32_t* group_array(const int32_t* group, int64_t group_key);
   // device eligibility mask live & allow (cached per mask_key and store version); null for null
   const uint8_t* eligibility(const uint8_t* allow, int64_t mask_key);
   // scan dtype: SR_DTYPE_F16 (default) or SR_DTYPE_FP8_E4M3 (fp8 copy + exact fp16 re-scoring)
@@ -147,6 +160,10 @@ class Store {
   int64_t version_ = 0, mask_key_ = 0, mask_version_ = -1, mask_rows_ = -1;
   // subset search: list offsets | list rows | query lists, groups and work items of one call
   DevBuf subset_;
+  // grouped search: the group array and what it was built from, the continuation rounds'
+  // eligibility mask (never the cached mask_), staging of one call, group_dev's per-query state
+  DevBuf group_, gmask_, gstage_, gstate_;
+  int64_t group_key_ = 0, group_version_ = -1, group_rows_ = -1;
 };
 
 // One collection row-sharded over several devices (store_set.cpp; C-ABI sr_store_set_*).

@@ -635,6 +635,138 @@ void Store::search_mmr_host(const float* q, int B, int k, int k_cand, float lamb
   for (size_t i = 0; i < nk; ++i) out_dist[i] = out_rows[i] >= 0 ? 1.0f - out_dist[i] : INFINITY;
 }
 
+const int32_t* Store::group_array(const int32_t* group, int64_t group_key) {
+  SR_CHECK(group != nullptr, "store.group: null group array");
+  // uploaded once per (group_key, store version), like the allow mask of eligibility()
+  if (group_key == 0 || group_key != group_key_ || group_version_ != version_ || group_rows_ != n_rows_) {
+    for (int64_t r = 0; r < n_rows_; ++r)
+      SR_CHECK(group[r] >= -1, "store.group: group ids must be >= -1 (-1: a group of its own)");
+    group_.reserve((size_t)std::max<int64_t>(n_rows_, 1) * sizeof(int32_t));
+    begin(stream_);
+    if (n_rows_ > 0)
+      SR_HIP(hipMemcpyAsync(group_.p, group, (size_t)n_rows_ * sizeof(int32_t), hipMemcpyHostToDevice,
+                            stream_));
+    SR_HIP(hipStreamSynchronize(stream_));
+    end(stream_);
+    group_key_ = group_key;
+    group_version_ = version_;
+    group_rows_ = n_rows_;
+  }
+  return group_.as<int32_t>();
+}
+
+void Store::group_dev(const int64_t* cand_rows, const float* cand_sims, int B, int K,
+                      int64_t row_offset, int k, int group_size, const int32_t* group,
+                      int64_t group_key, float* out_sim, int64_t* out_rows, int32_t* out_group,
+                      int32_t* out_complete, hipStream_t s) {
+  group_check_args(B, K, k, group_size);
+  if (B == 0) return;
+  SR_CHECK(cand_rows && cand_sims && out_sim && out_rows && out_group && out_complete,
+           "store.group: null buffer");
+  DeviceGuard g(device_);
+  const int32_t* dg = group_array(group, group_key);
+  // per-query state the continuation of search_grouped_host would read: found list | n_groups
+  const size_t nk = (size_t)B * k;
+  if (gstate_.bytes < nk * sizeof(uint64_t) + (size_t)B * sizeof(int32_t))
+    SR_HIP(hipEventSynchronize(done_));  // an earlier collapse may still write the old buffer
+  gstate_.reserve(nk * sizeof(uint64_t) + (size_t)B * sizeof(int32_t));
+  uint64_t* found = gstate_.as<uint64_t>();
+  int32_t* ng = reinterpret_cast<int32_t*>(found + nk);
+  begin(s);
+  launch_group_collapse(cand_sims, cand_rows, B, K, nullptr, nullptr, 0, row_offset, dg, n_rows_, k,
+                        group_size, out_sim, out_rows, out_group, ng, out_complete, found, nullptr,
+                        nullptr, s);
+  end(s);
+}
+
+void Store::search_grouped_host(const float* q, int B, int k, int group_size, int k_cand,
+                                const int32_t* group, int64_t group_key, const uint8_t* allow,
+                                int64_t mask_key, float* out_sim, int64_t* out_rows,
+                                int32_t* out_group) {
+  group_check_args(B, k_cand, k, group_size);
+  SR_CHECK(k_cand <= select_capacity() / 4, "store.search_grouped: k_cand too large");
+  if (B == 0) return;
+  SR_CHECK(q && group && out_sim && out_rows && out_group, "store.search_grouped: null buffer");
+  DeviceGuard g(device_);
+  const int32_t* dg = group_array(group, group_key);
+  const uint8_t* elig = eligibility(allow, mask_key);
+  // staging: queries | candidate rows | kept rows | carried rows x 2 | found lists | candidate sims |
+  // kept sims | carried sims x 2 | group ids | n_groups | complete
+  const size_t kg = (size_t)k * group_size;
+  const size_t nc = (size_t)B * k_cand, no = (size_t)B * kg, nk = (size_t)B * k;
+  const size_t qb = (size_t)round_up((int64_t)B * dim_ * sizeof(float), 16);
+  gstage_.reserve(qb + nc * 12 + no * 36 + nk * 12 + (size_t)B * 8);
+  float* dq = gstage_.as<float>();
+  int64_t* crows = reinterpret_cast<int64_t*>(gstage_.as<char>() + qb);
+  int64_t* orows = crows + nc;
+  int64_t* nrows[2] = {orows + no, orows + 2 * no};
+  uint64_t* found = reinterpret_cast<uint64_t*>(orows + 3 * no);
+  float* csim = reinterpret_cast<float*>(found + nk);
+  float* osim = csim + nc;
+  float* nsim[2] = {osim + no, osim + 2 * no};
+  int32_t* ogrp = reinterpret_cast<int32_t*>(osim + 3 * no);
+  int32_t* ng = ogrp + nk;
+  int32_t* comp = ng + B;
+
+  // round 0: the whole batch
+  SR_HIP(hipMemcpyAsync(dq, q, (size_t)B * dim_ * sizeof(float), hipMemcpyHostToDevice, stream_));
+  search_dev(dq, SR_DTYPE_F32, B, k_cand, csim, crows, 0, stream_, elig);
+  std::vector<int32_t> complete((size_t)B, 0);
+  begin(stream_);
+  launch_group_collapse(csim, crows, B, k_cand, nullptr, nullptr, 0, 0, dg, n_rows_, k, group_size,
+                        osim, orows, ogrp, ng, comp, found, nsim[0], nrows[0], stream_);
+  SR_HIP(hipMemcpyAsync(complete.data(), comp, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost,
+                        stream_));
+  end(stream_);
+  SR_HIP(hipStreamSynchronize(stream_));
+
+  // Continuation, one query at a time.  A round masks out the rows of the full groups (and, once k
+  // groups are found, "closed" mode, every row of any other group), scans the top k_cand of what is
+  // left and collapses it together with the carried rows of the full groups.  The rows of found but
+  // unfilled groups are not carried: they outrank everything else that stays eligible and head the
+  // new list by themselves.  Every carried row outranks the new list's tail (it was in an earlier
+  // top k_cand of a superset), so the union is an exact prefix of the walk.
+  // Termination: an incomplete round has a full list.  If its k_cand >= k * group_size rows all
+  // belong to kept groups that were not full before (an open round that ends with fewer than k groups,
+  // every closed round), fewer than k such groups share them, so one of them becomes full; full
+  // groups are carried and stay full, and k full groups are a complete result: at most k - 1 such
+  // rounds.  Only a round that ends with k groups found under an open mask (or round 0) may fill
+  // none, and it switches the query to closed mode for good: once.  So at most k rounds are
+  // incomplete, round 0 included, and the loop below runs at most k times; k + 1 is its hard bound.
+  const uint8_t* base = elig ? elig : live_.as<uint8_t>();
+  for (int b = 0; b < B; ++b) {
+    if (complete[(size_t)b]) continue;
+    gmask_.reserve((size_t)std::max<int64_t>(n_rows_, 1));
+    float* c_sim = csim + (size_t)b * k_cand;
+    int64_t* c_rows = crows + (size_t)b * k_cand;
+    int cur = 0;
+    for (int round = 1;; ++round) {
+      if (round > k + 1)
+        throw Error(SR_ERR_STATE, "store.search_grouped: continuation did not settle in k + 1 rounds");
+      begin(stream_);
+      launch_group_mask(base, dg, n_rows_, found + (size_t)b * k, ng + b, k, gmask_.as<uint8_t>(),
+                        stream_);
+      search_dev(dq + (size_t)b * dim_, SR_DTYPE_F32, 1, k_cand, c_sim, c_rows, 0, stream_,
+                 gmask_.as<uint8_t>());
+      launch_group_collapse(c_sim, c_rows, 1, k_cand, nsim[cur] + (size_t)b * kg,
+                            nrows[cur] + (size_t)b * kg, (int)kg, 0, dg, n_rows_, k, group_size,
+                            osim + (size_t)b * kg, orows + (size_t)b * kg, ogrp + (size_t)b * k, ng + b,
+                            comp + b, found + (size_t)b * k, nsim[cur ^ 1] + (size_t)b * kg,
+                            nrows[cur ^ 1] + (size_t)b * kg, stream_);
+      int32_t c = 0;
+      SR_HIP(hipMemcpyAsync(&c, comp + b, sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+      end(stream_);
+      SR_HIP(hipStreamSynchronize(stream_));
+      if (c) break;
+      cur ^= 1;
+    }
+  }
+  SR_HIP(hipMemcpyAsync(out_sim, osim, no * sizeof(float), hipMemcpyDeviceToHost, stream_));
+  SR_HIP(hipMemcpyAsync(out_rows, orows, no * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
+  SR_HIP(hipMemcpyAsync(out_group, ogrp, nk * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+  SR_HIP(hipStreamSynchronize(stream_));
+}
+
 // Snapshot format (little endian): "SRMISTO1", int32 dim, int64 n_rows, n_rows x dim fp16
 // (normalised rows, unpadded), n_rows bytes of live flags.  Written to "<path>.tmp", fsync'd and
 // renamed over <path>, so a crash mid-save leaves the previous snapshot intact.

@@ -31,6 +31,7 @@ SR_MAX_TOPK = 1024
 SR_MMR_ONEPASS = 0
 SR_MMR_GREEDY = 1
 SR_MMR_MAX_CAND = 128
+SR_GROUP_MAX_SIZE = 8
 
 
 class NativeUnavailableError(RuntimeError):
@@ -90,6 +91,11 @@ SIGNATURES = {
                                     c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "sr_store_search_subset": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p,
                                        c_void_p, c_void_p, c_void_p]),
+    "sr_store_search_grouped": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                                        c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "sr_store_group_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_int, c_int,
+                                   c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p]),
     "sr_store_set_scan_dtype": (c_int, [c_void_p, c_int]),
     "sr_store_save": (c_int, [c_void_p, c_char_p]),
     "sr_store_load": (c_int, [c_char_p, c_int, POINTER(c_void_p)]),

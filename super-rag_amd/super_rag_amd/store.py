@@ -240,6 +240,109 @@ class NativeStore:
                N.ptr(out_sim), N.ptr(out_rows), N.stream_handle(stream))
         return out_score, out_sim, out_rows
 
+    def _group_arg(self, group):
+        n, _ = self.count()
+        g = np.ascontiguousarray(np.asarray(group, dtype=np.int32))
+        if g.shape != (n,):
+            raise ValueError(f"group array must have {n} entries, got {g.shape}")
+        return g if n else np.zeros(1, dtype=np.int32)
+
+    def search_grouped(self, queries, k: int, group, group_size: int = 1, fetch_k: int | None = None,
+                       allow=None, mask_key: int = 0, group_key: int = 0, sim: bool = False):
+        """Grouped search (sr_store_search_grouped): the ``k`` best distinct groups of every query
+        with the ``group_size`` best rows of each, exact whatever ``fetch_k`` (the rows scanned per
+        round; default min(1024, max(4 k group_size, 64))).  ``group`` int32 [n_rows]: >= 0 a group,
+        -1 a group of its own; kept on the device while ``group_key`` != 0 and the store is
+        unchanged.  Returns (dist [B,k,g] fp32 = 1 - sim, +inf when missing, or with ``sim=True`` the
+        similarities, -inf when missing; rows [B,k,g] int64, -1 when missing; groups [B,k] int32,
+        -1 for an unfilled group slot): groups best first, a group's rows best first."""
+        q = np.ascontiguousarray(np.asarray(queries, dtype=np.float32))
+        if q.ndim == 1:
+            q = q[None]
+        if q.shape[1] != self.dim:
+            raise ValueError(f"query dim {q.shape[1]} != store dim {self.dim}")
+        B, k, gs = q.shape[0], int(k), int(group_size)
+        fetch = group_fetch_k(k, gs) if fetch_k is None else int(fetch_k)
+        g = self._group_arg(group)
+        a = None
+        if allow is not None:
+            n, _ = self.count()
+            a = np.ascontiguousarray(np.asarray(allow, dtype=np.uint8))
+            if a.shape != (n,):
+                raise ValueError(f"allow mask must have {n} entries, got {a.shape}")
+            if n == 0:
+                a = np.zeros(1, dtype=np.uint8)
+        shape = (B, max(k, 0), max(gs, 0))
+        s = np.empty(shape, dtype=np.float32)
+        rows = np.empty(shape, dtype=np.int64)
+        groups = np.empty(shape[:2], dtype=np.int32)
+        N.call("sr_store_search_grouped", self._h, N.ptr(q), B, k, gs, fetch, N.ptr(g), int(group_key),
+               N.ptr(a) if a is not None else None, int(mask_key) if a is not None else 0,
+               N.ptr(s), N.ptr(rows), N.ptr(groups))
+        if sim:
+            return np.where(rows >= 0, s, -np.inf).astype(np.float32), rows, groups
+        return (np.where(rows >= 0, np.float32(1.0) - s, np.float32(np.inf)).astype(np.float32), rows,
+                groups)
+
+    def group_dev(self, cand_rows, cand_sims, k: int, group, group_size: int = 1, group_key: int = 0,
+                  row_offset: int = 0, stream=None):
+        """Collapse candidates as search_dev wrote them (device tensors [B, K]) into the ``k`` best
+        groups with ``group_size`` rows each, no continuation (sr_store_group_dev).  Returns device
+        tensors (sim [B,k,g] fp32, rows [B,k,g] int64, groups [B,k] int32, complete [B] int32: 1
+        when the query's result is already exact)."""
+        import torch
+        assert cand_rows.is_cuda and cand_rows.is_contiguous() and cand_rows.dtype == torch.int64
+        assert cand_sims.is_cuda and cand_sims.is_contiguous() and cand_sims.dtype == torch.float32
+        assert cand_rows.shape == cand_sims.shape and cand_rows.dim() == 2
+        B, K = cand_rows.shape
+        k, gs = int(k), int(group_size)
+        g = self._group_arg(group)
+        dev = cand_rows.device
+        out_sim = torch.empty((B, max(k, 0), max(gs, 0)), dtype=torch.float32, device=dev)
+        out_rows = torch.empty((B, max(k, 0), max(gs, 0)), dtype=torch.int64, device=dev)
+        out_group = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
+        out_complete = torch.empty((B,), dtype=torch.int32, device=dev)
+        N.call("sr_store_group_dev", self._h, N.ptr(cand_rows), N.ptr(cand_sims), B, K, int(row_offset),
+               k, gs, N.ptr(g), int(group_key), N.ptr(out_sim), N.ptr(out_rows), N.ptr(out_group),
+               N.ptr(out_complete), N.stream_handle(stream))
+        return out_sim, out_rows, out_group, out_complete
+
+
+def group_fetch_k(k: int, group_size: int) -> int:
+    """Default rows scanned per round of a grouped search."""
+    return min(N.SR_MAX_TOPK, max(4 * int(k) * int(group_size), 64))
+
+
+def group_walk(sims, rows, group, k: int, group_size: int):
+    """The grouped-search walk on the host (ShardedStore's merge): ``sims`` / ``rows`` 1-D candidates
+    in any order (row < 0: missing), ``group`` indexed by row.  Rows are taken in (sim desc, row asc)
+    order; a row is kept while its group holds fewer than ``group_size`` rows and is a kept group or
+    fewer than ``k`` groups are.  Returns (sim [k,g] float64 -inf, rows [k,g] int64 -1, groups [k]
+    int32 -1)."""
+    sims = np.asarray(sims, dtype=np.float64).reshape(-1)
+    rows = np.asarray(rows, dtype=np.int64).reshape(-1)
+    ok = rows >= 0
+    sims, rows = sims[ok], rows[ok]
+    order = np.lexsort((rows, -sims))
+    out_s = np.full((k, group_size), -np.inf, dtype=np.float64)
+    out_r = np.full((k, group_size), -1, dtype=np.int64)
+    out_g = np.full(k, -1, dtype=np.int32)
+    seen = {}
+    for i in order.tolist():
+        r = int(rows[i])
+        g = int(group[r])
+        key = (r,) if g < 0 else g
+        at = seen.get(key)
+        if at is None:
+            if len(seen) >= k:
+                continue
+            at = seen[key] = [len(seen), 0]
+            out_g[at[0]] = g
+        if at[1] < group_size:
+            out_s[at[0], at[1]], out_r[at[0], at[1]] = sims[i], r
+            at[1] += 1
+    return out_s, out_r, out_g
+
 
 def pack_lists(lists):
     """Row lists -> CSR (list_off [n + 1] int64, list_rows int64), the layout of
@@ -548,6 +651,65 @@ class ShardedStore:
         if sim:
             return np.where(ok, s32, -np.inf).astype(np.float32), out_r
         return np.where(ok, np.float32(1.0) - s32, np.inf).astype(np.float32), out_r
+
+    def search_grouped(self, queries, k: int, group, group_size: int = 1, fetch_k: int | None = None,
+                       allow=None, mask_key: int = 0, group_key: int = 0, sim: bool = False):
+        """NativeStore.search_grouped over the shards: every shard searches with its slice of the
+        group array (global row order), and the per-shard results merge on the host by the same
+        walk over their union with global rows.  The merged GROUPS are exact (a group among the
+        collection's k best is among the k best of the shard that holds its best row), and so are
+        the rows for ``group_size`` 1.  A larger group's later rows may sit in a shard where the group
+        is not among the k best, so for ``group_size`` > 1 every query takes a second pass: each
+        shard searches only the rows of the query's k groups (an allow mask), which returns every
+        shard's best ``group_size`` rows of each of them, and the walk over that union is exact."""
+        q = np.ascontiguousarray(np.asarray(queries, dtype=np.float32))
+        if q.ndim == 1:
+            q = q[None]
+        if q.shape[1] != self.dim:
+            raise ValueError(f"query dim {q.shape[1]} != store dim {self.dim}")
+        B, k, gs = q.shape[0], int(k), int(group_size)
+        n = len(self.shard_of)
+        g = np.asarray(group, dtype=np.int32)
+        if g.shape != (n,):
+            raise ValueError(f"group array must have {n} entries, got {g.shape}")
+        sims, rows = [], []
+        for s, sh in enumerate(self.shards):
+            a = None if allow is None else np.asarray(allow, dtype=np.uint8)[self.tables[s]]
+            sm, r, _ = sh.search_grouped(q, k, g[self.tables[s]], group_size=gs, fetch_k=fetch_k,
+                                         allow=a, mask_key=mask_key, group_key=group_key, sim=True)
+            r = np.asarray(r).reshape(B, -1)
+            glob = np.where(r >= 0, self.tables[s][np.clip(r, 0, None)] if len(self.tables[s]) else -1, -1)
+            sims.append(np.asarray(sm).reshape(B, -1))
+            rows.append(glob)
+        S, R = np.concatenate(sims, 1), np.concatenate(rows, 1)
+        out_s = np.full((B, k, gs), -np.inf, dtype=np.float32)
+        out_r = np.full((B, k, gs), -1, dtype=np.int64)
+        out_g = np.full((B, k), -1, dtype=np.int32)
+        base = None if allow is None else np.asarray(allow, dtype=np.uint8) != 0
+        for b in range(B):
+            out_s[b], out_r[b], out_g[b] = group_walk(S[b], R[b], g, k, gs)
+            best = out_r[b, :, 0]
+            kb = int((best >= 0).sum())
+            if gs == 1 or kb == 0:
+                continue
+            # second pass: only the rows of this query's groups (and its ungrouped kept rows)
+            m = np.isin(g, out_g[b][(best >= 0) & (out_g[b] >= 0)])
+            m[best[(best >= 0) & (out_g[b] < 0)]] = True
+            if base is not None:
+                m &= base
+            s2, r2 = [], []
+            for s, sh in enumerate(self.shards):
+                sm, r, _ = sh.search_grouped(q[b:b + 1], kb, g[self.tables[s]], group_size=gs,
+                                             fetch_k=fetch_k, allow=m[self.tables[s]], mask_key=0,
+                                             group_key=group_key, sim=True)
+                r = np.asarray(r).reshape(-1)
+                r2.append(np.where(r >= 0, self.tables[s][np.clip(r, 0, None)] if len(self.tables[s]) else -1, -1))
+                s2.append(np.asarray(sm).reshape(-1))
+            out_s[b], out_r[b], out_g[b] = group_walk(np.concatenate(s2), np.concatenate(r2), g, k, gs)
+        if sim:
+            return out_s, out_r, out_g
+        return (np.where(out_r >= 0, np.float32(1.0) - out_s, np.float32(np.inf)).astype(np.float32),
+                out_r, out_g)
 
     @staticmethod
     def _merge_host(dists, rows, B, k):

@@ -25,6 +25,12 @@ equality / $in clause on such a field (filters.plan) is resolved to its row list
 ALL such items of a batch, whatever their filters, go to the device in one search_subset call that
 scores only those rows (k_subset.hip) instead of one masked full scan per distinct filter.  Same
 results; every other filter, diversified and hybrid / fulltext searches keep the mask path.
+Opt-in grouped search (ctx ``group_by=<metadata field>``, ``group_size``, ``group_fetch_k``, each
+overridable per call by a kwarg of the same name): ``top_k`` counts GROUPS (distinct values of the
+field, e.g. ``document_id``; a row without the field is a group of its own) and ``search`` returns
+the ``top_k`` best groups with the ``group_size`` best rows of each, exact, collapsed on the device
+(k_group.hip): group by group, best group first, a group's rows by distance ascending, at most
+``top_k * group_size`` documents.  Not combinable with ``diversify`` or ``hybrid``.
 Collections are process-wide (like a server): every connector object for the same collection
 name sees the same rows.  Row ids <-> uuid strings, texts and metadata live on the host; vectors
 live in HBM.  With ``ctx["snapshot_dir"]`` a collection is reloaded at construction and
@@ -159,6 +165,61 @@ class _Collection:
         # filter -> (version, resolved rows or None when the list is too long, the subset_max_rows
         # that decided it): LRU bounded by total rows
         self.subsets: "OrderedDict[str, tuple]" = OrderedDict()
+        # ctx "group_by": field -> {"ids": value -> int32 group id (hashable scalar values only),
+        # "rows": array('i') group id per row (-1: no such value, a group of its own; a tombstoned
+        # row keeps its id), "key" / "arr": serial key and numpy copy of the array the device caches},
+        # None until a connector asks
+        self.gindex: Optional[Dict[str, dict]] = None
+
+    def ensure_groups(self, field: str) -> None:
+        """Keep group ids of a metadata field, back-filling the rows added before."""
+        if self.gindex is None:
+            self.gindex = {}
+        if field not in self.gindex:
+            self.gindex[field] = {"ids": {}, "rows": array("i"), "key": 0, "arr": None}
+            self.group_rows(self.metadatas, [field])
+
+    def group_rows(self, metadatas, fields=None) -> None:
+        """Append the group ids of new rows (in row order) to every grouped field."""
+        if self.gindex is None:
+            return
+        from .filters import indexable
+        for f in (self.gindex if fields is None else fields):
+            gi = self.gindex[f]
+            ids, rows = gi["ids"], gi["rows"]
+            for md in metadatas:
+                v = md.get(f) if md else None
+                if v is not None and indexable(v):
+                    g = ids.get(v)
+                    if g is None:
+                        g = ids[v] = len(ids)
+                    rows.append(g)
+                else:
+                    rows.append(-1)
+            gi["arr"] = None
+
+    def remap_groups(self, remap) -> None:
+        """Renumber the per-row group ids through a compaction's old -> new row map (the kept rows
+        keep their order)."""
+        if self.gindex is None:
+            return
+        keep = np.asarray(remap, dtype=np.int64) >= 0
+        for gi in self.gindex.values():
+            old = np.array(gi["rows"], dtype=np.int32)
+            gi["rows"] = array("i", old[keep[:len(old)]].tolist())
+            gi["arr"] = None
+
+    def group_array(self, field: str):
+        """(serial key, int32 group id per row) of a grouped field: the key changes with the array,
+        so the store reuses its device copy while both are unchanged."""
+        gi = self.gindex[field]
+        if gi["arr"] is None:
+            gi["arr"] = np.array(gi["rows"], dtype=np.int32)
+            global _mask_serial
+            with _registry_lock:
+                _mask_serial += 1
+                gi["key"] = _mask_serial
+        return gi["key"], gi["arr"]
 
     def ensure_index(self, fields) -> None:
         """Index the named metadata fields, back-filling the rows added before."""
@@ -254,6 +315,7 @@ class _Collection:
                 from .lexical import analyze
                 self.lex.add([self.vocab.doc_ids(analyze(t)) for t in rec["texts"]])
             self.index_rows(len(self.ids), rec["metadatas"])
+            self.group_rows(rec["metadatas"])
             for u, t, m in zip(rec["ids"], rec["texts"], rec["metadatas"]):
                 self.row_of[u] = len(self.ids)
                 self.ids.append(u)
@@ -360,6 +422,16 @@ class MI355XVectorStoreConnector:
             fi = [fi]
         self.filter_index = [str(f) for f in fi] if fi and self.honor_filter else None
         self.subset_max_rows = int(ctx.get("subset_max_rows", SUBSET_MAX_ROWS))
+        # opt-in grouped search: top_k distinct values of a metadata field with the group_size best
+        # rows of each (k_group.hip); each key can be overridden per call by a kwarg of its name
+        self.group_by = ctx.get("group_by")
+        self.group_size = int(ctx.get("group_size", 1))
+        self.group_fetch_k = ctx.get("group_fetch_k")   # None: min(1024, max(4 top_k group_size, 64))
+        if self.group_by is not None and self.hybrid:
+            raise ValueError("hybrid and group_by cannot be combined (rrf scores are not cosines)")
+        if self.group_by is not None and self.diversify:
+            raise ValueError("diversify and group_by cannot be combined (MMR order is not a ranking "
+                             "to walk)")
         self.checkpoint_ratio = float(ctx.get("checkpoint_ratio", 1.0))
         self.store = self
         if self.snapshot_dir and _get(self.collection_name) is None:
@@ -372,6 +444,12 @@ class MI355XVectorStoreConnector:
         if c is not None:
             self._apply_scan_dtype(c)
             self._apply_filter_index(c)
+            self._apply_group_by(c)
+
+    def _apply_group_by(self, c: _Collection) -> None:
+        if self.group_by is not None:
+            with c.lock:
+                c.ensure_groups(str(self.group_by))
 
     def _apply_filter_index(self, c: _Collection) -> None:
         if self.filter_index:
@@ -398,6 +476,7 @@ class MI355XVectorStoreConnector:
                 _collections[self.collection_name] = c
         self._apply_scan_dtype(c)
         self._apply_filter_index(c)
+        self._apply_group_by(c)
         return c
 
     def create_collection(self, **kwargs: Any):
@@ -443,6 +522,7 @@ class MI355XVectorStoreConnector:
                 c.texts.append(n.text)
                 c.metadatas.append(copy.deepcopy(n.metadata) if n.metadata is not None else None)
             c.index_rows(first, c.metadatas[first:])
+            c.group_rows(c.metadatas[first:])
             c.version += 1
             c.persist_add(first, vecs, ids, c.texts[first:], c.metadatas[first:])
             c.maybe_checkpoint(self.checkpoint_ratio)
@@ -480,6 +560,7 @@ class MI355XVectorStoreConnector:
             lremap = c.lex.compact()
             assert np.array_equal(np.asarray(lremap), np.asarray(remap)), "lexical remap differs"
         c.remap_index(remap)
+        c.remap_groups(remap)
         keep = [i for i, r in enumerate(remap) if r >= 0]
         c.ids = [c.ids[i] for i in keep]
         c.texts = [c.texts[i] for i in keep]
@@ -514,8 +595,36 @@ class MI355XVectorStoreConnector:
                              f"candidates")
         return lam, mode, max(int(fetch), int(top_k))
 
+    def _group_params(self, kwargs, top_k: int):
+        """None (group_by off: the search item stays the tuple it is today) or the (field,
+        group_size, fetch_k) of this call: ctx keys, each overridden by a kwarg of its name."""
+        field = kwargs.get("group_by", self.group_by)
+        if field is None:
+            return None
+        if self.hybrid:
+            raise ValueError("hybrid and group_by cannot be combined (rrf scores are not cosines)")
+        if kwargs.get("diversify", self.diversify) is not None:
+            raise ValueError("diversify and group_by cannot be combined (MMR order is not a ranking "
+                             "to walk)")
+        from ._native import SR_GROUP_MAX_SIZE, SR_MAX_TOPK as cap
+        size = int(kwargs.get("group_size", self.group_size))
+        if not 1 <= size <= SR_GROUP_MAX_SIZE:
+            raise ValueError(f"group_size must be in [1, {SR_GROUP_MAX_SIZE}], got {size}")
+        need = int(top_k) * size
+        if need > cap:
+            raise ValueError(f"group_by: top_k {int(top_k)} x group_size {size} exceeds the cap of "
+                             f"{cap} rows")
+        fetch = kwargs.get("group_fetch_k", self.group_fetch_k)
+        if fetch is None:
+            fetch = min(cap, max(4 * need, 64))
+        elif int(fetch) > cap:
+            raise ValueError(f"group_by: group_fetch_k {int(fetch)} exceeds the cap of {cap} rows")
+        return str(field), size, max(int(fetch), need)
+
     @staticmethod
-    def _item(q, k: int, flt, mmr):
+    def _item(q, k: int, flt, mmr, grp=None):
+        if grp is not None:
+            return (q, k, flt, None, grp)
         return (q, k, flt) if mmr is None else (q, k, flt, mmr)
 
     def search(self, query, **kwargs):
@@ -525,6 +634,7 @@ class MI355XVectorStoreConnector:
         q = np.asarray(query.embedding, dtype=np.float32)
         flt = kwargs.get("filter") if self.honor_filter else None
         thr = kwargs.get("score_threshold") if self.honor_score_threshold else None
+        grp = self._group_params(kwargs, query.top_k)
         mmr = self._mmr_params(kwargs, query.top_k)
         if self.hybrid:
             # rrf of the dense and the BM25 rankings on the device; score = rrf score (desc)
@@ -532,9 +642,9 @@ class MI355XVectorStoreConnector:
                                results=self._hybrid(c, q, query.query or "", int(query.top_k), flt))
         if self.coalesce:
             # concurrent single-query searches share one device batch (coalesce.py)
-            results = self._coalescer(c)(self._item(q, int(query.top_k), flt, mmr))
+            results = self._coalescer(c)(self._item(q, int(query.top_k), flt, mmr, grp))
         else:
-            results = self._search_batch(c, [self._item(q, int(query.top_k), flt, mmr)])[0]
+            results = self._search_batch(c, [self._item(q, int(query.top_k), flt, mmr, grp)])[0]
         return QueryResult(query=query.query, results=self._threshold(results, thr))
 
     async def asearch(self, query, **kwargs):
@@ -547,8 +657,9 @@ class MI355XVectorStoreConnector:
         q = np.asarray(query.embedding, dtype=np.float32)
         flt = kwargs.get("filter") if self.honor_filter else None
         thr = kwargs.get("score_threshold") if self.honor_score_threshold else None
+        grp = self._group_params(kwargs, query.top_k)
         mmr = self._mmr_params(kwargs, query.top_k)
-        results = await self._coalescer(c).acall(self._item(q, int(query.top_k), flt, mmr))
+        results = await self._coalescer(c).acall(self._item(q, int(query.top_k), flt, mmr, grp))
         return QueryResult(query=query.query, results=self._threshold(results, thr))
 
     def can_fuse_embed(self, embedding_model) -> bool:
@@ -582,7 +693,8 @@ class MI355XVectorStoreConnector:
             return QueryResult(query=text, results=[])
         flt = kwargs.get("filter") if self.honor_filter else None
         thr = kwargs.get("score_threshold") if self.honor_score_threshold else None
-        item = self._item(text.replace("\n", " "), int(top_k), flt, self._mmr_params(kwargs, top_k))
+        grp = self._group_params(kwargs, top_k)
+        item = self._item(text.replace("\n", " "), int(top_k), flt, self._mmr_params(kwargs, top_k), grp)
         results = await self._text_coalescer(c, embedding_model).acall(item)
         return QueryResult(query=text, results=self._threshold(results, thr))
 
@@ -684,12 +796,20 @@ class MI355XVectorStoreConnector:
         return hasattr(store, "search_subset")
 
     @staticmethod
+    def _has_grouped(store) -> bool:
+        shards = getattr(store, "shards", None)
+        if shards is not None:
+            return all(hasattr(sh, "search_grouped") for sh in shards)
+        return hasattr(store, "search_grouped")
+
+    @staticmethod
     def _search_batch(c: _Collection, items) -> List[List[DocumentWithScore]]:
-        """[(query vector, top_k, filter[, (mmr lambda, mode, fetch_k)])] -> per query
-        [DocumentWithScore] (distance asc, or MMR order for a diversified item; no ids).  With a
-        field index, every undiversified item whose filter resolves to a row list goes to the store
-        in ONE search_subset call (items with the same filter share a list); the other queries
-        share one device search per filter and MMR setting."""
+        """[(query vector, top_k, filter[, (mmr lambda, mode, fetch_k)[, (group field, group_size,
+        fetch_k)]])] -> per query [DocumentWithScore] (distance asc, MMR order for a diversified
+        item, group by group for a grouped one; no ids).  With a field index, every undiversified,
+        ungrouped item whose filter resolves to a row list goes to the store in ONE search_subset
+        call (items with the same filter share a list); the other queries share one device search
+        per filter and MMR / grouping setting."""
         out: List[List[DocumentWithScore]] = [[] for _ in items]
         groups: Dict[tuple, list] = {}
         with c.lock:
@@ -699,7 +819,8 @@ class MI355XVectorStoreConnector:
                 flt = it[2]
                 fkey = "" if flt is None else json.dumps(flt, sort_keys=True, default=str)
                 mmr = it[3] if len(it) > 3 else None
-                if use_subset and flt is not None and mmr is None:
+                grp = it[4] if len(it) > 4 else None
+                if use_subset and flt is not None and mmr is None and grp is None:
                     li = list_of.get(fkey)
                     if li is None:
                         rows = MI355XVectorStoreConnector._subset_rows(c, flt)
@@ -710,7 +831,7 @@ class MI355XVectorStoreConnector:
                         sub_idx.append(i)
                         sub_list.append(li)
                         continue
-                groups.setdefault((fkey, mmr), []).append(i)
+                groups.setdefault((fkey, mmr) if grp is None else (fkey, mmr, grp), []).append(i)
             if sub_idx:
                 Q = np.stack([np.asarray(items[i][0], dtype=np.float32).reshape(-1) for i in sub_idx])
                 kmax = max(items[i][1] for i in sub_idx)
@@ -722,12 +843,35 @@ class MI355XVectorStoreConnector:
                     out[i] = [_make_doc(text=c.texts[r], score=float(d),
                                         metadata=_json_copy(c.metadatas[r]))
                               for d, r in zip(dist[j, :k].tolist(), rows[j, :k].tolist()) if r >= 0]
-            for (key, mmr), idx in groups.items():
+            for gkey_, idx in groups.items():
+                key, mmr = gkey_[0], gkey_[1]
+                grp = gkey_[2] if len(gkey_) > 2 else None
                 Q = np.stack([np.asarray(items[i][0], dtype=np.float32).reshape(-1) for i in idx])
                 kmax = max(items[i][1] for i in idx)
                 allow, mkey = None, 0
                 if key != "":
                     mkey, allow = MI355XVectorStoreConnector._allow_mask(c, items[idx[0]][2])
+                if grp is not None:
+                    field, size, fetch_k = grp
+                    if not MI355XVectorStoreConnector._has_grouped(c.store):
+                        raise RuntimeError(f"group_by needs a store with search_grouped; "
+                                           f"{type(c.store).__name__} has none")
+                    c.ensure_groups(field)
+                    gkey, garr = c.group_array(field)
+                    with devices_gate(_store_devices(c.store), "search"):
+                        dist, rows, _ = c.store.search_grouped(
+                            Q, kmax, garr, group_size=size, fetch_k=max(fetch_k, kmax * size),
+                            allow=allow, mask_key=mkey, group_key=gkey)
+                    # [B, k, g] -> the first k groups, group by group (rows of a group: distance asc)
+                    dist = np.asarray(dist).reshape(len(idx), -1)
+                    rows = np.asarray(rows).reshape(len(idx), -1)
+                    for j, i in enumerate(idx):
+                        n_out = items[i][1] * size
+                        out[i] = [_make_doc(text=c.texts[r], score=float(d),
+                                            metadata=_json_copy(c.metadatas[r]))
+                                  for d, r in zip(dist[j, :n_out].tolist(), rows[j, :n_out].tolist())
+                                  if r >= 0]
+                    continue
                 if mmr is not None:
                     lam, mode, fetch_k = mmr
                     with devices_gate(_store_devices(c.store), "search"):
