@@ -354,6 +354,73 @@ int sr_hybrid_search(sr_store* s, sr_lex* x, const float* q, const int64_t* qoff
                      double* out_score, int64_t* out_rows);
 
 /* ------------------------------------------------------------------------------------------------
+ * Score-based fusion (Weaviate relativeScoreFusion, Milvus WeightedRanker, min-max linear
+ * combination; Bruch et al. 2023): the alternative to rrf that keeps the scores (k_fuse.hip).
+ * Per query two scored lists: a = (score_a [ka] fp32, rows_a [ka] int64) and b likewise with kb.
+ * An entry with row < 0 is absent wherever it stands; a row appears at most once per list; no
+ * order is assumed; the scores of present entries are finite.  side_a [kb] (optional): the a-metric
+ * score of each b row, for example the exact cosine of a BM25 hit; -inf = unknown.
+ * Semantics, fp32, every operation rounded once (no FMA contraction), correctly rounded division:
+ *   hi    = max of the present scores of the list itself (-inf for an empty list); side_a never
+ *           enters hi or lo
+ *   lo    = SR_FUSE_MINMAX: min of the present scores of the list (+inf for an empty list);
+ *           SR_FUSE_FLOOR: the caller's floor_a / floor_b
+ *   score = a row's a-score is list a's value when the row is in list a, else side_a of its b entry
+ *           (unknown without side_a or for -inf); its b-score is list b's value or unknown
+ *   norm(s) = hi > lo ? max(0, (s - lo) / (hi - lo)) : 1 for a known score, 0 for an unknown one
+ *   fused = (alpha * norm_a) + (one_minus_alpha * norm_b), one_minus_alpha = 1.0f - alpha
+ * Output: the first k_out distinct rows by (fused desc, row asc), the store's tie rule (not rrf's
+ * "first appearance"); rows with fused < min_score are dropped; unfilled slots hold -inf / -1.
+ * out_a / out_b (optional, B x k_out): the a- and b-score of each kept row as used above (side_a
+ * included), -inf where unknown.
+ * Limits: ka, kb in [0, 2048]; k_out in [1, 2048]; alpha in [0, 1]; rows in [0, 2^32 - 2] (checked by
+ * the host variant; the device variant reads whatever it is given without indexing anything by
+ * it).  B == 0 is a no-op; anything else, a null buffer or an unknown mode is SR_ERR_INVALID before
+ * any device call.
+ * Not provided: an sr_store_set_* counterpart (the Python ShardedLex fuses the merged lists),
+ * fusion with grouped / diversified / subset search, and any claim about retrieval quality.
+ * ---------------------------------------------------------------------------------------------- */
+#define SR_FUSE_MINMAX 0 /* "relative": lo = the list's own minimum */
+#define SR_FUSE_FLOOR 1  /* "floor": lo = floor_a / floor_b, the metric's theoretical minimum */
+
+/* Host buffers, blocking; computed on `device`. */
+int sr_score_fuse(const float* score_a, const int64_t* rows_a, int ka, const float* score_b,
+                  const int64_t* rows_b, int kb, const float* side_a, int B, int mode, float alpha,
+                  float floor_a, float floor_b, float min_score, int k_out, float* out_score,
+                  int64_t* out_rows, float* out_a, float* out_b, int device);
+/* Same on device buffers, asynchronous on `stream` of `device`. */
+int sr_score_fuse_dev(const float* score_a, const int64_t* rows_a, int ka, const float* score_b,
+                      const int64_t* rows_b, int kb, const float* side_a, int B, int mode,
+                      float alpha, float floor_a, float floor_b, float min_score, int k_out,
+                      float* out_score, int64_t* out_rows, float* out_a, float* out_b, int device,
+                      void* stream);
+
+/* Exact cosine of given (query, row) pairs on the fp16 rows (either scan dtype): out_sim[b, j] =
+ * q_b . x_rows[b, j] with the query normalised as a search normalises it and fp32 accumulation;
+ * -inf for a row < 0, a row >= n_rows or a tombstoned row (checked before anything is indexed).
+ * q: B x dim host fp32; rows: B x K host int64; blocking.  B or K == 0 is a no-op. */
+int sr_store_score_rows(sr_store* s, const float* q, int B, const int64_t* rows, int K,
+                        float* out_sim);
+/* Device buffers (q_dtype as in sr_store_search_dev; rows carry row_offset); asynchronous on
+ * `stream`. */
+int sr_store_score_rows_dev(sr_store* s, const void* q, int q_dtype, int B, const int64_t* rows,
+                            int K, int64_t row_offset, float* out_sim, void* stream);
+
+/* sr_hybrid_search with score fusion as its last step: list a = the dense top-k_each with its
+ * cosines, list b = the BM25 top-k_each with its scores, fused by sr_score_fuse semantics into
+ * B x k (k in [1, 2 k_each], k_each in [1, SR_MAX_TOPK]); out_score fp32 fused scores, out_dense /
+ * out_lex (optional) the components.  SR_FUSE_MINMAX passes no side scores.  SR_FUSE_FLOOR uses
+ * floor_a = -1 (cosine), floor_b = 0 (BM25) and completes the dense side: side_a = the exact
+ * cosines (sr_store_score_rows semantics) of the BM25 list's rows.  The BM25 side is NOT completed
+ * for dense-only rows (the index keeps no per-row offsets into its forward postings): a row that
+ * shares no term with the query has BM25 exactly 0, which is the floor, so only a row that matches
+ * but was truncated from the BM25 top-k_each is under-scored, by less than that list's minimum. */
+int sr_hybrid_search_fused(sr_store* s, sr_lex* x, const float* q, const int64_t* qoff,
+                           const int32_t* qterms, int B, int k, int k_each, int mode, float alpha,
+                           float min_score, const uint8_t* allow, int64_t mask_key,
+                           float* out_score, int64_t* out_rows, float* out_dense, float* out_lex);
+
+/* ------------------------------------------------------------------------------------------------
  * Transformer encoder (BERT / XLM-R family: bge-small/base-en, bge-m3, bge-reranker-*)
  * Weights are set by Hugging Face tensor name without the model prefix, e.g.
  * "embeddings.word_embeddings.weight", "encoder.layer.3.attention.self.query.weight",

@@ -800,6 +800,177 @@ int sr_hybrid_search(sr_store* s, sr_lex* x, const float* q, const int64_t* qoff
   SR_API_END
 }
 
+// ---- score fusion (k_fuse.hip) ---------------------------------------------------------------------
+static void fuse_check_buffers(const float* score_a, const int64_t* rows_a, int ka, const float* score_b,
+                        const int64_t* rows_b, int kb, const float* out_score,
+                        const int64_t* out_rows) {
+  SR_CHECK(out_score && out_rows, "score_fuse: null output buffer");
+  SR_CHECK(ka == 0 || (score_a && rows_a), "score_fuse: null list a");
+  SR_CHECK(kb == 0 || (score_b && rows_b), "score_fuse: null list b");
+}
+
+int sr_score_fuse(const float* score_a, const int64_t* rows_a, int ka, const float* score_b,
+                  const int64_t* rows_b, int kb, const float* side_a, int B, int mode, float alpha,
+                  float floor_a, float floor_b, float min_score, int k_out, float* out_score,
+                  int64_t* out_rows, float* out_a, float* out_b, int device) {
+  SR_API_BEGIN
+  sr::fuse_check_args(B, ka, kb, mode, alpha, k_out);
+  if (B == 0) return SR_OK;
+  fuse_check_buffers(score_a, rows_a, ka, score_b, rows_b, kb, out_score, out_rows);
+  for (int64_t i = 0; i < (int64_t)B * ka; ++i)
+    SR_CHECK(rows_a[i] <= 0xfffffffeLL, "score_fuse: rows must be in [0, 2^32 - 2] (or < 0: absent)");
+  for (int64_t i = 0; i < (int64_t)B * kb; ++i)
+    SR_CHECK(rows_b[i] <= 0xfffffffeLL, "score_fuse: rows must be in [0, 2^32 - 2] (or < 0: absent)");
+  sr::DeviceGuard g(device);
+  // staging: rows a | rows b | out rows | score a | score b | side a | out score | out a | out b
+  const size_t na = (size_t)B * ka, nb = (size_t)B * kb, no = (size_t)B * k_out;
+  sr::DevBuf ws;
+  ws.reserve((na + nb + no) * 8 + (na + 2 * nb + 3 * no) * 4 + 8);
+  int64_t* da_r = ws.as<int64_t>();
+  int64_t* db_r = da_r + na;
+  int64_t* do_r = db_r + nb;
+  float* da_s = reinterpret_cast<float*>(do_r + no);
+  float* db_s = da_s + na;
+  float* dside = db_s + nb;
+  float* do_s = dside + nb;
+  float* do_a = do_s + no;
+  float* do_b = do_a + no;
+  hipStream_t st = nullptr;
+  SR_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+  try {
+    if (na) {
+      SR_HIP(hipMemcpyAsync(da_r, rows_a, na * 8, hipMemcpyHostToDevice, st));
+      SR_HIP(hipMemcpyAsync(da_s, score_a, na * 4, hipMemcpyHostToDevice, st));
+    }
+    if (nb) {
+      SR_HIP(hipMemcpyAsync(db_r, rows_b, nb * 8, hipMemcpyHostToDevice, st));
+      SR_HIP(hipMemcpyAsync(db_s, score_b, nb * 4, hipMemcpyHostToDevice, st));
+      if (side_a) SR_HIP(hipMemcpyAsync(dside, side_a, nb * 4, hipMemcpyHostToDevice, st));
+    }
+    sr::launch_score_fuse(da_s, da_r, ka, db_s, db_r, kb, side_a ? dside : nullptr, B, mode, alpha,
+                          floor_a, floor_b, min_score, k_out, do_s, do_r, out_a ? do_a : nullptr,
+                          out_b ? do_b : nullptr, st);
+    SR_HIP(hipMemcpyAsync(out_score, do_s, no * 4, hipMemcpyDeviceToHost, st));
+    SR_HIP(hipMemcpyAsync(out_rows, do_r, no * 8, hipMemcpyDeviceToHost, st));
+    if (out_a) SR_HIP(hipMemcpyAsync(out_a, do_a, no * 4, hipMemcpyDeviceToHost, st));
+    if (out_b) SR_HIP(hipMemcpyAsync(out_b, do_b, no * 4, hipMemcpyDeviceToHost, st));
+    SR_HIP(hipStreamSynchronize(st));
+  } catch (...) {
+    (void)hipStreamSynchronize(st);
+    (void)hipStreamDestroy(st);
+    throw;
+  }
+  SR_HIP(hipStreamDestroy(st));
+  SR_API_END
+}
+
+int sr_score_fuse_dev(const float* score_a, const int64_t* rows_a, int ka, const float* score_b,
+                      const int64_t* rows_b, int kb, const float* side_a, int B, int mode,
+                      float alpha, float floor_a, float floor_b, float min_score, int k_out,
+                      float* out_score, int64_t* out_rows, float* out_a, float* out_b, int device,
+                      void* stream) {
+  SR_API_BEGIN
+  sr::fuse_check_args(B, ka, kb, mode, alpha, k_out);
+  if (B == 0) return SR_OK;
+  fuse_check_buffers(score_a, rows_a, ka, score_b, rows_b, kb, out_score, out_rows);
+  sr::DeviceGuard g(device);
+  sr::launch_score_fuse(score_a, rows_a, ka, score_b, rows_b, kb, side_a, B, mode, alpha, floor_a,
+                        floor_b, min_score, k_out, out_score, out_rows, out_a, out_b,
+                        reinterpret_cast<hipStream_t>(stream));
+  SR_API_END
+}
+
+int sr_store_score_rows(sr_store* s, const float* q, int B, const int64_t* rows, int K,
+                        float* out_sim) {
+  SR_API_BEGIN
+  SR_NONNULL(s);
+  SR_CHECK(B >= 0 && K >= 0, "store.score_rows: negative shape");
+  if (B == 0 || K == 0) return SR_OK;
+  SR_NONNULL(q);
+  SR_NONNULL(rows);
+  SR_NONNULL(out_sim);
+  std::lock_guard<std::mutex> lk(s->impl->mu);
+  s->impl->score_rows_host(q, B, rows, K, out_sim);
+  SR_API_END
+}
+
+int sr_store_score_rows_dev(sr_store* s, const void* q, int q_dtype, int B, const int64_t* rows,
+                            int K, int64_t row_offset, float* out_sim, void* stream) {
+  SR_API_BEGIN
+  SR_NONNULL(s);
+  SR_CHECK(B >= 0 && K >= 0, "store.score_rows: negative shape");
+  SR_CHECK(q_dtype == SR_DTYPE_F32 || q_dtype == SR_DTYPE_F16,
+           "store.score_rows: query dtype must be fp32 or fp16");
+  if (B == 0 || K == 0) return SR_OK;
+  SR_NONNULL(q);
+  SR_NONNULL(rows);
+  SR_NONNULL(out_sim);
+  std::lock_guard<std::mutex> lk(s->impl->mu);
+  s->impl->score_rows_dev(q, q_dtype, B, rows, K, row_offset, out_sim,
+                          reinterpret_cast<hipStream_t>(stream));
+  SR_API_END
+}
+
+int sr_hybrid_search_fused(sr_store* s, sr_lex* x, const float* q, const int64_t* qoff,
+                           const int32_t* qterms, int B, int k, int k_each, int mode, float alpha,
+                           float min_score, const uint8_t* allow, int64_t mask_key,
+                           float* out_score, int64_t* out_rows, float* out_dense, float* out_lex) {
+  SR_API_BEGIN
+  SR_CHECK(B >= 0, "hybrid: negative batch");
+  SR_CHECK(k_each >= 1 && k_each <= SR_MAX_TOPK, "hybrid: k_each must be in [1, 1024]");
+  SR_CHECK(k >= 1 && k <= 2 * k_each, "hybrid: k must be in [1, 2 * k_each]");
+  sr::fuse_check_args(B, k_each, k_each, mode, alpha, k);
+  SR_NONNULL(s);
+  SR_NONNULL(x);
+  if (B == 0) return SR_OK;
+  SR_NONNULL(q);
+  SR_NONNULL(qoff);
+  SR_NONNULL(out_score);
+  SR_NONNULL(out_rows);
+  std::scoped_lock lk(s->impl->mu, x->impl->mu);
+  sr::Store& st = *s->impl;
+  sr::LexIndex& lx = *x->impl;
+  SR_CHECK(st.device() == lx.device(), "hybrid: store and lexical index on different devices");
+  int64_t lrows = 0;
+  lx.stats(&lrows, nullptr, nullptr, nullptr, nullptr);
+  SR_CHECK(lrows == st.rows(), "hybrid: store and lexical index hold different row counts");
+  sr::DeviceGuard g(st.device());
+  hipStream_t sm = lx.stream();
+  // staging: queries | dense rows | lex rows | out rows | dense sims | lex scores | side | out x 3
+  const size_t bq = (size_t)sr::round_up((int64_t)B * st.dim() * 4, 16);
+  const size_t ne = (size_t)B * k_each, no = (size_t)B * k;
+  sr::DevBuf ws;
+  ws.reserve(bq + (2 * ne + no) * 8 + (3 * ne + 3 * no) * 4 + 64);
+  char* w = ws.as<char>();
+  float* dq = reinterpret_cast<float*>(w);
+  int64_t* drow = reinterpret_cast<int64_t*>(w + bq);
+  int64_t* lrow = drow + ne;
+  int64_t* orow = lrow + ne;
+  float* dsim = reinterpret_cast<float*>(orow + no);
+  float* lsc = dsim + ne;
+  float* side = lsc + ne;
+  float* os = side + ne;
+  float* oa = os + no;
+  float* ob = oa + no;
+  const bool floor_mode = mode == SR_FUSE_FLOOR;
+  const uint8_t* elig = st.eligibility(allow, mask_key);
+  lx.begin(sm);
+  SR_HIP(hipMemcpyAsync(dq, q, (size_t)B * st.dim() * 4, hipMemcpyHostToDevice, sm));
+  st.search_dev(dq, SR_DTYPE_F32, B, k_each, dsim, drow, 0, sm, elig);
+  lx.search_dev(qoff, qterms, B, k_each, allow, mask_key, lsc, lrow, sm);
+  if (floor_mode) st.score_rows_dev(dq, SR_DTYPE_F32, B, lrow, k_each, 0, side, sm);
+  sr::launch_score_fuse(dsim, drow, k_each, lsc, lrow, k_each, floor_mode ? side : nullptr, B, mode,
+                        alpha, -1.0f, 0.0f, min_score, k, os, orow, out_dense ? oa : nullptr,
+                        out_lex ? ob : nullptr, sm);
+  SR_HIP(hipMemcpyAsync(out_score, os, no * 4, hipMemcpyDeviceToHost, sm));
+  SR_HIP(hipMemcpyAsync(out_rows, orow, no * 8, hipMemcpyDeviceToHost, sm));
+  if (out_dense) SR_HIP(hipMemcpyAsync(out_dense, oa, no * 4, hipMemcpyDeviceToHost, sm));
+  if (out_lex) SR_HIP(hipMemcpyAsync(out_lex, ob, no * 4, hipMemcpyDeviceToHost, sm));
+  lx.end(sm);
+  SR_HIP(hipStreamSynchronize(sm));
+  SR_API_END
+}
+
 int sr_encoder_create(const sr_encoder_config* cfg, int device, sr_encoder** out) {
   SR_API_BEGIN
   SR_NONNULL(cfg);

@@ -246,6 +246,23 @@ void launch_group_mask(const uint8_t* base, const int32_t* group, int64_t n_rows
                        const uint64_t* found, const int32_t* n_groups, int k, uint8_t* out,
                        hipStream_t s);
 
+// k_fuse.hip — score fusion of two scored row lists per query (one workgroup each; the function is
+// stated in include/super_rag_mi355x.h): lists (score, rows) of ka / kb entries, row < 0 absent,
+// side_a [B][kb] optional a-scores of the b rows; outputs B x k_out by (fused desc, row asc),
+// -inf / -1 unfilled, out_a / out_b optional components.  fuse_check_args throws SR_ERR_INVALID
+// outside the documented limits.  launch_score_rows: out[b][j] = qn_b . row (rows[b][j] - row_offset)
+// over the fp16 rows (qn [B][ld] normalised, zero padded), -inf for a row outside [0, n_rows) or with
+// live == 0; one wave per pair.
+void fuse_check_args(int B, int ka, int kb, int mode, float alpha, int k_out);
+void launch_score_fuse(const float* score_a, const int64_t* rows_a, int ka, const float* score_b,
+                       const int64_t* rows_b, int kb, const float* side_a, int B, int mode,
+                       float alpha, float floor_a, float floor_b, float min_score, int k_out,
+                       float* out_score, int64_t* out_rows, float* out_a, float* out_b,
+                       hipStream_t s);
+void launch_score_rows(const half_t* corpus, int ld, int64_t n_rows, const uint8_t* live,
+                       const half_t* qn, const int64_t* rows, int B, int K, int64_t row_offset,
+                       float* out, hipStream_t s);
+
 // k_lex.hip — reciprocal-rank fusion of two ranked row lists per query (-1 padded), fp64 scores.
 void launch_rrf_fuse(const int64_t* rows_a, int ka, const int64_t* rows_b, int kb, int B,
                      int rank_const, double min_score, int k_out, double* out_score,

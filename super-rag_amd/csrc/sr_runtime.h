@@ -114,6 +114,11 @@ class Store {
                  int64_t* out_rows, int32_t* out_group, int32_t* out_complete, hipStream_t s);
   // device copy of a host group array (validated; cached per group_key and store version)
   const int32_t* group_array(const int32_t* group, int64_t group_key);
+  // exact cosines of (query, row) pairs on the fp16 rows (k_fuse.hip score_rows): rows [B][K] carry
+  // row_offset; -inf for a row outside the store or tombstoned; asynchronous on s
+  void score_rows_dev(const void* q, int q_dtype, int B, const int64_t* rows, int K,
+                      int64_t row_offset, float* out_sim, hipStream_t s);
+  void score_rows_host(const float* q, int B, const int64_t* rows, int K, float* out_sim);
   // device eligibility mask live & allow (cached per mask_key and store version); null for null
   const uint8_t* eligibility(const uint8_t* allow, int64_t mask_key);
   // scan dtype: SR_DTYPE_F16 (default) or SR_DTYPE_FP8_E4M3 (fp8 copy + exact fp16 re-scoring)

@@ -767,6 +767,39 @@ void Store::search_grouped_host(const float* q, int B, int k, int group_size, in
   SR_HIP(hipStreamSynchronize(stream_));
 }
 
+void Store::score_rows_dev(const void* q, int q_dtype, int B, const int64_t* rows, int K,
+                           int64_t row_offset, float* out_sim, hipStream_t s) {
+  SR_CHECK(B >= 0 && K >= 0, "store.score_rows: negative shape");
+  if (B == 0 || K == 0) return;
+  SR_CHECK(q && rows && out_sim, "store.score_rows: null buffer");
+  DeviceGuard g(device_);
+  begin(s);
+  ensure_query_ws(B);
+  half_t* qn = qbuf_.as<half_t>();
+  launch_normalize_rows(q, q_dtype, B, dim_, qn, ld_, s);
+  launch_score_rows(corpus_.as<half_t>(), ld_, n_rows_, live_.as<uint8_t>(), qn, rows, B, K,
+                    row_offset, out_sim, s);
+  end(s);
+}
+
+void Store::score_rows_host(const float* q, int B, const int64_t* rows, int K, float* out_sim) {
+  SR_CHECK(B >= 0 && K >= 0, "store.score_rows: negative shape");
+  if (B == 0 || K == 0) return;
+  SR_CHECK(q && rows && out_sim, "store.score_rows: null buffer");
+  DeviceGuard g(device_);
+  const size_t qb = (size_t)round_up((int64_t)B * dim_ * sizeof(float), 16);
+  const size_t nk = (size_t)B * K;
+  qstage_.reserve(qb + nk * (sizeof(int64_t) + sizeof(float)));
+  float* dq = qstage_.as<float>();
+  int64_t* drows = reinterpret_cast<int64_t*>(qstage_.as<char>() + qb);
+  float* dsim = reinterpret_cast<float*>(drows + nk);
+  SR_HIP(hipMemcpyAsync(dq, q, (size_t)B * dim_ * sizeof(float), hipMemcpyHostToDevice, stream_));
+  SR_HIP(hipMemcpyAsync(drows, rows, nk * sizeof(int64_t), hipMemcpyHostToDevice, stream_));
+  score_rows_dev(dq, SR_DTYPE_F32, B, drows, K, 0, dsim, stream_);
+  SR_HIP(hipMemcpyAsync(out_sim, dsim, nk * sizeof(float), hipMemcpyDeviceToHost, stream_));
+  SR_HIP(hipStreamSynchronize(stream_));
+}
+
 // Snapshot format (little endian): "SRMISTO1", int32 dim, int64 n_rows, n_rows x dim fp16
 // (normalised rows, unpadded), n_rows bytes of live flags.  Written to "<path>.tmp", fsync'd and
 // renamed over <path>, so a crash mid-save leaves the previous snapshot intact.

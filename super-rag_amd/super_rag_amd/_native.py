@@ -32,6 +32,8 @@ SR_MMR_ONEPASS = 0
 SR_MMR_GREEDY = 1
 SR_MMR_MAX_CAND = 128
 SR_GROUP_MAX_SIZE = 8
+SR_FUSE_MINMAX = 0
+SR_FUSE_FLOOR = 1
 
 
 class NativeUnavailableError(RuntimeError):
@@ -136,6 +138,18 @@ SIGNATURES = {
                                 c_void_p, c_void_p, c_int, c_void_p]),
     "sr_hybrid_search": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                  c_int, c_int, c_double, c_void_p, c_int64, c_void_p, c_void_p]),
+    "sr_score_fuse": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                              c_int, c_float, c_float, c_float, c_float, c_int, c_void_p, c_void_p,
+                              c_void_p, c_void_p, c_int]),
+    "sr_score_fuse_dev": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                                  c_int, c_int, c_float, c_float, c_float, c_float, c_int, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "sr_store_score_rows": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "sr_store_score_rows_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int64,
+                                        c_void_p, c_void_p]),
+    "sr_hybrid_search_fused": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                       c_int, c_int, c_int, c_float, c_float, c_void_p, c_int64,
+                                       c_void_p, c_void_p, c_void_p, c_void_p]),
     "sr_topk_merge_dev": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
                                   c_void_p, c_int, c_void_p]),
     "sr_encoder_create": (c_int, [POINTER(EncoderConfigC), c_int, POINTER(c_void_p)]),

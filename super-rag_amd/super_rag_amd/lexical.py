@@ -11,7 +11,9 @@ The reference declares the pieces but ships no backend: a ``fulltext_search`` no
   * ``NativeLexIndex``: the device BM25 index (k_lex.hip): Okapi BM25, k1 = 1.2, b = 0.75, Lucene's
     idf ln(1 + (N - df + 0.5) / (df + 0.5)) over live rows, scores in 2^-16 fixed point;
   * ``rrf_fuse`` / ``hybrid_search``: reciprocal-rank fusion as graphiti's ``rrf``
-    (graphiti_core/search/search_utils.py:1762-1778), on the device.
+    (graphiti_core/search/search_utils.py:1762-1778), on the device;
+  * ``score_fuse`` / ``hybrid_search(fusion="relative" | "floor")``: score-based fusion (weighted
+    min-max or floor-normalised cosine + BM25, k_fuse.hip), opt-in next to rrf.
 There is no CPU fallback: every entry point needs the HIP library and a GPU.
 """
 from __future__ import annotations
@@ -283,10 +285,11 @@ class NativeLexIndex:
         return score, rows
 
     def hybrid(self, store, queries, query_terms, k: int, k_each: Optional[int] = None,
-               rank_const: int = 1, min_score: float = float("-inf"), allow=None, mask_key: int = 0):
+               rank_const: int = 1, min_score: float = float("-inf"), allow=None, mask_key: int = 0,
+               fusion: str = "rrf", alpha: float = 0.5):
         """hybrid_search over (store, this index)."""
         return hybrid_search(store, self, queries, query_terms, k, k_each, rank_const, min_score,
-                             allow, mask_key)
+                             allow, mask_key, fusion=fusion, alpha=alpha)
 
 
 class ShardedLex:
@@ -410,13 +413,27 @@ class ShardedLex:
         return out_s, out_r
 
     def hybrid(self, store, queries, query_terms, k: int, k_each: Optional[int] = None,
-               rank_const: int = 1, min_score: float = float("-inf"), allow=None, mask_key: int = 0):
+               rank_const: int = 1, min_score: float = float("-inf"), allow=None, mask_key: int = 0,
+               fusion: str = "rrf", alpha: float = 0.5):
         """Dense top-k_each over the sharded store and BM25 top-k_each over these shards, fused by
-        rrf (sr_hybrid_search's three steps on a sharded collection)."""
+        rrf (sr_hybrid_search's three steps on a sharded collection) or, with ``fusion`` "relative"
+        / "floor", by score (sr_hybrid_search_fused's steps).  Score fusion works on the MERGED
+        lists: the dense side merges on similarities (ShardedStore.search_sim), the normalisation
+        sees the collection's lists, never a shard's, and "floor" completes the dense side through
+        ShardedStore.score_rows, so the result equals a single-device collection's bit for bit."""
+        mode = fusion_mode(fusion)
         k_each = int(k_each or k)
-        _, dense = store.search(queries, k_each, allow=allow, mask_key=mask_key)
-        _, lex = self.search(query_terms, k_each, allow=allow, mask_key=mask_key)
-        return _rrf_rows(dense, lex, k, rank_const, min_score, self.devices[0])
+        if mode is None:
+            _, dense = store.search(queries, k_each, allow=allow, mask_key=mask_key)
+            _, lex = self.search(query_terms, k_each, allow=allow, mask_key=mask_key)
+            return _rrf_rows(dense, lex, k, rank_const, min_score, self.devices[0])
+        check_alpha(alpha)
+        sims, dense = store.search_sim(queries, k_each, allow=allow, mask_key=mask_key)
+        lsc, lex = self.search(query_terms, k_each, allow=allow, mask_key=mask_key)
+        side = store.score_rows(queries, lex) if mode == N.SR_FUSE_FLOOR else None
+        score, rows, _, _ = _fuse_rows(sims, dense, lsc, lex, side, mode, alpha, -1.0, 0.0,
+                                       min_score, k, self.devices[0])
+        return score, rows
 
     def save(self, path: str) -> None:
         import json
@@ -452,6 +469,34 @@ class ShardedLex:
 def _rrf_rows(rows_a, rows_b, k, rank_const, min_score, device):
     """rrf of two host row lists on the device (rrf_fuse), or through the test seam."""
     return _rrf_impl[0](rows_a, rows_b, k, rank_const, min_score, device)
+
+
+def _fuse_rows(score_a, rows_a, score_b, rows_b, side_a, mode, alpha, floor_a, floor_b, min_score, k,
+               device):
+    """score_fuse of two host lists on the device, or through the test seam."""
+    return _fuse_impl[0](score_a, rows_a, score_b, rows_b, side_a, mode, alpha, floor_a, floor_b,
+                         min_score, k, device)
+
+
+FUSIONS = ("rrf", "relative", "floor")
+
+
+def fusion_mode(fusion: str):
+    """Fusion name -> None for "rrf", else the SR_FUSE_* mode; ValueError for an unknown name."""
+    if fusion == "rrf":
+        return None
+    if fusion == "relative":
+        return N.SR_FUSE_MINMAX
+    if fusion == "floor":
+        return N.SR_FUSE_FLOOR
+    raise ValueError(f"unsupported fusion '{fusion}' (one of {', '.join(FUSIONS)})")
+
+
+def check_alpha(alpha) -> float:
+    a = float(alpha)
+    if not 0.0 <= a <= 1.0:
+        raise ValueError(f"alpha must be in [0, 1] (the weight of the dense side), got {alpha}")
+    return a
 
 
 def _dev_i32(t):
@@ -491,17 +536,94 @@ def rrf_fuse_dev(rows_a, rows_b, k: int, rank_const: int = 1, min_score: float =
     return scores, rows
 
 
+def score_fuse(score_a, rows_a, score_b, rows_b, k: int, mode: str = "relative", alpha: float = 0.5,
+               side_a=None, floor_a: float = -1.0, floor_b: float = 0.0,
+               min_score: float = float("-inf"), device: int = 0):
+    """Device score fusion of two scored row lists per query (sr_score_fuse; host arrays score
+    [B, ka] fp32 / rows [B, ka] int64 and the same with kb; row < 0 = absent; ``side_a`` [B, kb]:
+    the a-metric score of each b row, -inf = unknown).  ``mode``: "relative" (min-max of each
+    list) or "floor" (lo = floor_a / floor_b).  Returns (fused [B,k] fp32 desc, rows [B,k] int64,
+    a [B,k] fp32, b [B,k] fp32): -inf / -1 / -inf / -inf in unfilled slots."""
+    m = fusion_mode(mode) if isinstance(mode, str) else int(mode)
+    if m is None:
+        raise ValueError("score_fuse: mode must be 'relative' or 'floor'")
+    N.require_gpu()
+    ra = np.ascontiguousarray(np.asarray(rows_a, dtype=np.int64))
+    rb = np.ascontiguousarray(np.asarray(rows_b, dtype=np.int64))
+    Bq = ra.shape[0]
+    sa = np.ascontiguousarray(np.asarray(score_a, dtype=np.float32).reshape(ra.shape))
+    sb = np.ascontiguousarray(np.asarray(score_b, dtype=np.float32).reshape(rb.shape))
+    assert ra.ndim == 2 and rb.ndim == 2 and rb.shape[0] == Bq
+    sd = None
+    if side_a is not None:
+        sd = np.ascontiguousarray(np.asarray(side_a, dtype=np.float32).reshape(rb.shape))
+    ka, kb = ra.shape[1], rb.shape[1]
+    k = int(k)
+    out = [np.empty((Bq, max(k, 0)), dtype=t) for t in (np.float32, np.int64, np.float32, np.float32)]
+    N.call("sr_score_fuse", N.ptr(sa) if ka and Bq else None, N.ptr(ra) if ka and Bq else None, ka,
+           N.ptr(sb) if kb and Bq else None, N.ptr(rb) if kb and Bq else None, kb,
+           N.ptr(sd) if (sd is not None and kb and Bq) else None, Bq, m, float(alpha), float(floor_a),
+           float(floor_b), float(min_score), k, N.ptr(out[0]), N.ptr(out[1]), N.ptr(out[2]),
+           N.ptr(out[3]), int(device))
+    return tuple(out)
+
+
+def score_fuse_dev(score_a, rows_a, score_b, rows_b, k: int, mode: str = "relative",
+                   alpha: float = 0.5, side_a=None, floor_a: float = -1.0, floor_b: float = 0.0,
+                   min_score: float = float("-inf"), stream=None):
+    """score_fuse on device tensors (torch fp32 / int64 [B, ka], [B, kb]; sr_score_fuse_dev),
+    asynchronous on ``stream`` -> device tensors (fused, rows, a, b) [B, k]."""
+    import torch
+    m = fusion_mode(mode) if isinstance(mode, str) else int(mode)
+    if m is None:
+        raise ValueError("score_fuse_dev: mode must be 'relative' or 'floor'")
+    ra, rb = rows_a.contiguous(), rows_b.contiguous()
+    sa, sb = score_a.contiguous(), score_b.contiguous()
+    assert ra.is_cuda and ra.dtype == torch.int64 and rb.dtype == torch.int64
+    assert sa.dtype == torch.float32 and sb.dtype == torch.float32
+    assert sa.shape == ra.shape and sb.shape == rb.shape and ra.dim() == 2 and rb.shape[0] == ra.shape[0]
+    sd = None
+    if side_a is not None:
+        sd = side_a.contiguous()
+        assert sd.dtype == torch.float32 and sd.shape == rb.shape
+    Bq, k = ra.shape[0], int(k)
+    dev = ra.device
+    out = [torch.empty((Bq, max(k, 0)), dtype=t, device=dev)
+           for t in (torch.float32, torch.int64, torch.float32, torch.float32)]
+    N.call("sr_score_fuse_dev", N.ptr(sa), N.ptr(ra), ra.shape[1], N.ptr(sb), N.ptr(rb), rb.shape[1],
+           None if sd is None else N.ptr(sd), Bq, m, float(alpha), float(floor_a), float(floor_b),
+           float(min_score), k, N.ptr(out[0]), N.ptr(out[1]), N.ptr(out[2]), N.ptr(out[3]),
+           dev.index or 0, N.stream_handle(stream))
+    return tuple(out)
+
+
 def hybrid_search(store, lex: NativeLexIndex, queries, query_terms: Sequence[Sequence[int]], k: int,
                   k_each: Optional[int] = None, rank_const: int = 1,
-                  min_score: float = float("-inf"), allow=None, mask_key: int = 0):
-    """Dense top-k_each (cosine, store) and BM25 top-k_each (lex) fused by rrf on the device ->
-    (rrf score [B,k] fp64 desc, rows [B,k] int64)."""
+                  min_score: float = float("-inf"), allow=None, mask_key: int = 0,
+                  fusion: str = "rrf", alpha: float = 0.5, components: bool = False):
+    """Dense top-k_each (cosine, store) and BM25 top-k_each (lex) fused on the device.
+    ``fusion`` "rrf" (default): reciprocal rank -> (rrf score [B,k] fp64 desc, rows [B,k] int64).
+    "relative" / "floor": score fusion (sr_hybrid_search_fused) with ``alpha`` the weight of the
+    dense side -> (fused score [B,k] fp32 desc, rows [B,k] int64), and with ``components`` also the
+    cosine and the BM25 score of each kept row (-inf where unknown)."""
+    mode = fusion_mode(fusion)
     q = np.ascontiguousarray(np.asarray(queries, dtype=np.float32))
     if q.ndim == 1:
         q = q[None]
     Bq = q.shape[0]
     assert len(query_terms) == Bq
     k_each = int(k_each or k)
+    if mode is not None:
+        check_alpha(alpha)
+        out = [np.empty((Bq, k), dtype=t) for t in (np.float32, np.int64, np.float32, np.float32)]
+        if Bq:
+            qoff, qterms = query_arrays(query_terms)
+            a = None if allow is None else _mask(allow, store.count()[0])
+            N.call("sr_hybrid_search_fused", store._h, lex._h, N.ptr(q), N.ptr(qoff), N.ptr(qterms),
+                   Bq, int(k), k_each, mode, float(alpha), float(min_score),
+                   None if a is None else N.ptr(a), int(mask_key), N.ptr(out[0]), N.ptr(out[1]),
+                   N.ptr(out[2]), N.ptr(out[3]))
+        return tuple(out) if components else (out[0], out[1])
     scores = np.empty((Bq, k), dtype=np.float64)
     rows = np.empty((Bq, k), dtype=np.int64)
     if Bq == 0:
@@ -517,6 +639,20 @@ def hybrid_search(store, lex: NativeLexIndex, queries, query_terms: Sequence[Seq
 _rrf_impl = [lambda a, b, k, rc, ms, dev: rrf_fuse(a, b, k, rc, ms, dev)]
 
 
+def _fuse_native(sa, ra, sb, rb, side, mode, alpha, fa, fb, ms, k, dev):
+    return score_fuse(sa, ra, sb, rb, k, mode, alpha, side, fa, fb, ms, dev)
+
+
+_fuse_impl = [_fuse_native]
+
+
 def set_rrf_backend(fn) -> None:
     """Test seam: replace the host-list rrf used by ShardedLex.hybrid (CPU doubles)."""
     _rrf_impl[0] = fn or (lambda a, b, k, rc, ms, dev: rrf_fuse(a, b, k, rc, ms, dev))
+
+
+def set_fuse_backend(fn) -> None:
+    """Test seam: replace the host-list score fusion used by ShardedLex.hybrid (CPU doubles);
+    fn(score_a, rows_a, score_b, rows_b, side_a, mode, alpha, floor_a, floor_b, min_score, k,
+    device) -> (fused, rows, a, b)."""
+    _fuse_impl[0] = fn or _fuse_native

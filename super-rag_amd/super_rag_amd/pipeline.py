@@ -101,7 +101,8 @@ class SearchPipeline:
                  passage_tok: torch.Tensor, passage_len: torch.Tensor, k_candidates: int = 100,
                  k_final: int = 10, pair_len: int = 128, shard_offset: int = 0, group=None,
                  merge_fn=topk_merge_dev, lexical=None, k_each: int | None = None,
-                 rank_const: int = 1, force_exchange: bool = False, shard_passages: bool = False):
+                 rank_const: int = 1, force_exchange: bool = False, shard_passages: bool = False,
+                 fusion: str = "rrf", alpha: float = 0.5):
         self.embedder = embedder
         self.reranker = reranker
         self.store = store
@@ -124,6 +125,16 @@ class SearchPipeline:
         self.exchange = self.world > 1 or bool(force_exchange)
         # passage_tok / passage_len hold only rows [shard_offset, shard_offset + len) (C3 fetch)
         self.shard_passages = bool(shard_passages) and self.exchange
+        # hybrid fusion: "rrf" (default), or score fusion (k_fuse.hip) "relative" / "floor" with alpha
+        # the weight of the dense side.  "floor" completes the dense side with the cosines of the
+        # BM25 rows, which this rank can read only while every candidate row is its own
+        from .lexical import check_alpha, fusion_mode
+        self.fusion = str(fusion)
+        self.fuse_mode = fusion_mode(self.fusion)
+        self.alpha = check_alpha(alpha)
+        if self.fusion == "floor" and self.exchange:
+            raise ValueError("fusion 'floor' needs every candidate row on this rank: not available "
+                             "with an exchange (world > 1 or force_exchange); use 'relative'")
         self.clock: StageClock | None = None   # set a StageClock to time the stages of run()
 
     def _mark(self, stage, like):
@@ -169,12 +180,12 @@ class SearchPipeline:
         return out
 
     def retrieve_hybrid(self, q_emb: torch.Tensor, q_tok: torch.Tensor, q_len: torch.Tensor):
-        """Dense top-k_each + BM25 top-k_each (query tokens) fused by rrf -> (rrf score, rows)
-        [B, K] of this rank's queries.  Everything stays on the device: the query tokens go to the
-        lexical kernels as a padded [B, Lq] matrix (sr_lex_search_tok_dev), and sharded, the
+        """Dense top-k_each + BM25 top-k_each (query tokens) fused by rrf, or by score with
+        ``fusion`` "relative" / "floor" -> (fused score, rows) [B, K] of this rank's queries.
+        Everything stays on the device: the query tokens go to the lexical kernels as a padded [B, Lq] matrix (sr_lex_search_tok_dev), and sharded, the
         corpus-wide N, summed length and per-(query, position) df are one device vector
         (sr_lex_query_stats_dev) summed by one all_reduce (RCCL) before scoring."""
-        from .lexical import rrf_fuse_dev
+        from .lexical import rrf_fuse_dev, score_fuse_dev
         B = q_emb.shape[0]
         dev = q_emb.device
         ke = self.k_each
@@ -211,9 +222,18 @@ class SearchPipeline:
             host = dist.get_backend(self.group) == "gloo" and q_emb.is_cuda
             sims, rows = self._exchange(sims, rows, B, ke, host, dev)
             lsc, lrows = self._exchange(lsc, lrows, B, ke, host, dev)
-        score, fused = rrf_fuse_dev(rows, lrows, self.K, self.rank_const)
+        if self.fuse_mode is None:
+            score, fused = rrf_fuse_dev(rows, lrows, self.K, self.rank_const)
+            self._mark("search", score)
+            return score.float(), fused
+        side = None
+        if self.fusion == "floor":   # (no exchange here: allq is q_emb and every row is local)
+            side = self.store.score_rows_dev(allq.contiguous(), lrows.contiguous(),
+                                             row_offset=self.offset)
+        score, fused, _, _ = score_fuse_dev(sims, rows, lsc, lrows, self.K, self.fusion, self.alpha,
+                                            side_a=side)
         self._mark("search", score)
-        return score.float(), fused
+        return score, fused
 
     def passages(self, cand_rows: torch.Tensor):
         """(token table, lengths, [B, K] indices into them) for this rank's candidates (global

@@ -240,6 +240,39 @@ class NativeStore:
                N.ptr(out_sim), N.ptr(out_rows), N.stream_handle(stream))
         return out_score, out_sim, out_rows
 
+    def score_rows(self, queries, rows) -> np.ndarray:
+        """Exact cosine of given (query, row) pairs on the fp16 rows (sr_store_score_rows): queries
+        [B, dim], rows [B, K] int64 -> sim [B, K] fp32, -inf for a row < 0, a row outside the store
+        or a tombstoned row.  The same value in either scan mode."""
+        q = np.ascontiguousarray(np.asarray(queries, dtype=np.float32))
+        if q.ndim == 1:
+            q = q[None]
+        if q.shape[1] != self.dim:
+            raise ValueError(f"query dim {q.shape[1]} != store dim {self.dim}")
+        r = np.ascontiguousarray(np.asarray(rows, dtype=np.int64))
+        if r.ndim != 2 or r.shape[0] != q.shape[0]:
+            raise ValueError(f"rows must be [{q.shape[0]}, K], got {r.shape}")
+        out = np.empty(r.shape, dtype=np.float32)
+        if r.size:
+            N.call("sr_store_score_rows", self._h, N.ptr(q), q.shape[0], N.ptr(r), r.shape[1],
+                   N.ptr(out))
+        return out
+
+    def score_rows_dev(self, q, rows, row_offset: int = 0, out=None, stream=None):
+        """score_rows on device tensors: q [B, dim] fp16/fp32 as search_dev takes it, rows [B, K]
+        int64 carrying ``row_offset`` -> sim [B, K] fp32 device tensor (sr_store_score_rows_dev)."""
+        import torch
+        assert q.is_cuda and q.is_contiguous() and q.shape[1] == self.dim
+        assert rows.is_cuda and rows.is_contiguous() and rows.dtype == torch.int64
+        assert rows.dim() == 2 and rows.shape[0] == q.shape[0]
+        dt = N.SR_DTYPE_F16 if q.dtype == torch.float16 else N.SR_DTYPE_F32
+        if out is None:
+            out = torch.empty(tuple(rows.shape), dtype=torch.float32, device=q.device)
+        if rows.numel():
+            N.call("sr_store_score_rows_dev", self._h, N.ptr(q), dt, q.shape[0], N.ptr(rows),
+                   rows.shape[1], int(row_offset), N.ptr(out), N.stream_handle(stream))
+        return out
+
     def _group_arg(self, group):
         n, _ = self.count()
         g = np.ascontiguousarray(np.asarray(group, dtype=np.int32))
@@ -593,6 +626,49 @@ class ShardedStore:
         if allow is None and all(hasattr(sh, "search_dev") for sh in self.shards):
             return self._search_device(q, int(k))
         return self._search_host(q, int(k), allow, mask_key)
+
+    def search_sim(self, queries, k: int, allow=None, mask_key: int = 0):
+        """search() returning (sim [B,k] fp32 descending, -inf when missing; rows [B,k]): every
+        shard's search_sim merged on the host by (similarity desc, global row asc), the single
+        store's list bit for bit (search() reports 1 - sim, which cannot be turned back)."""
+        q = np.ascontiguousarray(np.asarray(queries, dtype=np.float32))
+        if q.ndim == 1:
+            q = q[None]
+        if q.shape[1] != self.dim:
+            raise ValueError(f"query dim {q.shape[1]} != store dim {self.dim}")
+        B, k = q.shape[0], int(k)
+        keys, rows = [], []
+        for s, sh in enumerate(self.shards):
+            a = None if allow is None else np.asarray(allow, dtype=np.uint8)[self.tables[s]]
+            sim, r = sh.search_sim(q, k, allow=a, mask_key=mask_key)
+            g = np.where(r >= 0, self.tables[s][np.clip(r, 0, None)] if len(self.tables[s]) else -1, -1)
+            keys.append(np.where(g >= 0, -np.asarray(sim, np.float64), np.inf))
+            rows.append(g)
+        out_d, out_r = self._merge_host(keys, rows, B, k)
+        return np.where(out_r >= 0, (-out_d).astype(np.float32), -np.inf).astype(np.float32), out_r
+
+    def score_rows(self, queries, rows) -> np.ndarray:
+        """NativeStore.score_rows with global rows: every pair goes to the shard that owns its row
+        (the routing tables); -inf for a row < 0, outside the collection or tombstoned."""
+        q = np.ascontiguousarray(np.asarray(queries, dtype=np.float32))
+        if q.ndim == 1:
+            q = q[None]
+        r = np.asarray(rows, dtype=np.int64)
+        if r.ndim != 2 or r.shape[0] != q.shape[0]:
+            raise ValueError(f"rows must be [{q.shape[0]}, K], got {r.shape}")
+        n = len(self.shard_of)
+        ok = (r >= 0) & (r < n)
+        safe = np.where(ok, r, 0)
+        owner = np.where(ok, self.shard_of[safe] if n else -1, -1)
+        out = np.full(r.shape, -np.inf, dtype=np.float32)
+        for s, sh in enumerate(self.shards):
+            mine = owner == s
+            if not mine.any():
+                continue
+            local = np.where(mine, self.local_of[safe] if n else -1, -1)
+            got = np.asarray(sh.score_rows(q, local), dtype=np.float32)
+            out[mine] = got[mine]
+        return out
 
     def search_mmr(self, queries, k: int, fetch_k: int, lam: float = 0.5, mode: str = "onepass",
                    min_score: float = -2.0, allow=None, mask_key: int = 0):

@@ -12,7 +12,9 @@ Mirrors SeekDBVectorStoreConnector (super_rag/vectorstore/seekdb_connector.py:31
 Opt-in lexical retrieval (ctx ``fulltext``): every added node's text is also indexed for BM25 on
 the device (lexical.py, k_lex.hip); ``fulltext_search(text, top_k, keywords)`` backs the
 reference's ``fulltext_search`` node type, and ctx ``hybrid`` makes ``search`` fuse the dense and
-the BM25 rankings by reciprocal rank on the device (score = rrf score, descending).  Both work on
+the BM25 rankings by reciprocal rank on the device (score = rrf score, descending) or, with ctx
+``hybrid_fusion`` "relative" / "floor" and ``hybrid_alpha`` (the weight of the dense side), by their
+normalised scores (k_fuse.hip; score = fused score, descending).  Both work on
 collections sharded over several devices (ctx ``devices``: lexical.ShardedLex, corpus-wide BM25
 statistics), with the same results as one device.
 Opt-in diversification (ctx ``diversify="mmr"``, ``mmr_lambda``, ``mmr_mode``, ``mmr_fetch_k``, each
@@ -404,6 +406,12 @@ class MI355XVectorStoreConnector:
         self.fulltext = bool(ctx.get("fulltext", False)) or self.hybrid
         self.hybrid_k_each = ctx.get("hybrid_k_each")
         self.rrf_rank_const = int(ctx.get("rrf_rank_const", 1))
+        # opt-in score fusion (k_fuse.hip): "relative" (min-max of each list) or "floor" (cosine from
+        # -1, BM25 from 0, dense side completed); hybrid_alpha = the weight of the dense side
+        from .lexical import check_alpha, fusion_mode
+        self.hybrid_fusion = str(ctx.get("hybrid_fusion", "rrf"))
+        fusion_mode(self.hybrid_fusion)          # ValueError for an unknown name
+        self.hybrid_alpha = check_alpha(ctx.get("hybrid_alpha", 0.5))
         self.scan_dtype = str(ctx.get("scan_dtype", "fp16"))   # "fp8": e4m3 scan + fp16 re-score
         # opt-in diversification: MMR over the top mmr_fetch_k rows on the device (k_mmr.hip);
         # each key can be overridden per call by a search kwarg of the same name
@@ -902,8 +910,11 @@ class MI355XVectorStoreConnector:
             if flt is not None:
                 mkey, allow = self._allow_mask(c, flt)
             with devices_gate(_store_devices(c.store), "search"):
+                # (the default passes no fusion keyword: the rrf call is the one it always was)
+                fuse = {} if self.hybrid_fusion == "rrf" else {"fusion": self.hybrid_fusion,
+                                                               "alpha": self.hybrid_alpha}
                 scores, rows = c.lex.hybrid(c.store, q.reshape(1, -1), [terms], k, k_each,
-                                            self.rrf_rank_const, allow=allow, mask_key=mkey)
+                                            self.rrf_rank_const, allow=allow, mask_key=mkey, **fuse)
             return [_make_doc(text=c.texts[r], score=float(s), metadata=_json_copy(c.metadatas[r]))
                     for s, r in zip(scores[0].tolist(), rows[0].tolist()) if r >= 0]
 
