@@ -328,6 +328,26 @@ int sr_lex_query_stats_dev(sr_lex* x, const int32_t* tok, const int32_t* qlen, i
 int sr_lex_search_tok_dev(sr_lex* x, const int32_t* tok, const int32_t* qlen, int B, int Lq, int k,
                           const int64_t* gstats, float* out_score, int64_t* out_rows,
                           int64_t row_offset, void* stream);
+/* Exact BM25 of given (query, row) pairs, sr_store_score_rows' lexical twin (k_lex.hip
+ * lex_score_rows): out_score[b, j] = the score sr_lex_search gives row rows[b, j] for query b, from
+ * the row's own forward postings (the index keeps foff[rows + 1], the first posting of each row).
+ * The scored terms, their multiplicities, idf and avgdl are the search's (distinct query terms with
+ * 0 <= t < vocabulary and live df > 0; this index's statistics, or `global`: a query term missing
+ * from its table is the search's error), the sum is the same order-independent 2^-16 fixed point:
+ * out_fixed (optional, B x K uint32) equals sr_lex_search_global_fixed's value for the same pair
+ * bit for bit and out_score = (float)out_fixed / 65536.  A row < 0, >= n_rows or tombstoned gives
+ * -inf / 0 (checked before anything is indexed by it); a live row that shares no scored term gives
+ * 0.0f / 0.  Host queries as for sr_lex_search; rows: B x K host int64; blocking.  B == 0 or K == 0 is
+ * a no-op; argument errors are SR_ERR_INVALID before any device work.  Triggers the pending rebuild
+ * of the inverted index (df comes from it). */
+int sr_lex_score_rows(sr_lex* x, const int64_t* qoff, const int32_t* qterms, int B,
+                      const int64_t* rows, int K, const sr_lex_global* global, float* out_score,
+                      uint32_t* out_fixed);
+/* Device rows (B x K int64 carrying row_offset) and device outputs (out_fixed may be NULL), on
+ * `stream`, which is synchronised once for the host-built term tables, as sr_lex_search_dev does. */
+int sr_lex_score_rows_dev(sr_lex* x, const int64_t* qoff, const int32_t* qterms, int B,
+                          const int64_t* rows, int K, const sr_lex_global* global,
+                          int64_t row_offset, float* out_score, uint32_t* out_fixed, void* stream);
 int sr_lex_save(sr_lex* x, const char* path);
 int sr_lex_load(const char* path, int device, sr_lex** out);
 int sr_lex_compact(sr_lex* x, int64_t* old_to_new);
@@ -382,6 +402,9 @@ int sr_hybrid_search(sr_store* s, sr_lex* x, const float* q, const int64_t* qoff
  * ---------------------------------------------------------------------------------------------- */
 #define SR_FUSE_MINMAX 0 /* "relative": lo = the list's own minimum */
 #define SR_FUSE_FLOOR 1  /* "floor": lo = floor_a / floor_b, the metric's theoretical minimum */
+#define SR_FUSE_FLOOR_FULL 2 /* "floor_full": SR_FUSE_FLOOR with BOTH sides completed; accepted by
+                                sr_hybrid_search_fused only (sr_score_fuse* reject it: pass
+                                SR_FUSE_FLOOR and side_b to sr_score_fuse_sides*) */
 
 /* Host buffers, blocking; computed on `device`. */
 int sr_score_fuse(const float* score_a, const int64_t* rows_a, int ka, const float* score_b,
@@ -394,6 +417,23 @@ int sr_score_fuse_dev(const float* score_a, const int64_t* rows_a, int ka, const
                       float alpha, float floor_a, float floor_b, float min_score, int k_out,
                       float* out_score, int64_t* out_rows, float* out_a, float* out_b, int device,
                       void* stream);
+
+/* sr_score_fuse with the mirror of side_a: side_b [ka] (optional) is the b-metric score of each a
+ * row, for example the exact BM25 (sr_lex_score_rows) of a dense hit; -inf = unknown.  It is used
+ * only for a row that list b does not hold (its b-score is then side_b of its a entry instead of
+ * unknown), never enters hi_b / lo_b, and shows in out_b.  side_b == NULL is sr_score_fuse bit for
+ * bit.  Same limits and errors. */
+int sr_score_fuse_sides(const float* score_a, const int64_t* rows_a, int ka, const float* score_b,
+                        const int64_t* rows_b, int kb, const float* side_a, const float* side_b,
+                        int B, int mode, float alpha, float floor_a, float floor_b, float min_score,
+                        int k_out, float* out_score, int64_t* out_rows, float* out_a, float* out_b,
+                        int device);
+int sr_score_fuse_sides_dev(const float* score_a, const int64_t* rows_a, int ka,
+                            const float* score_b, const int64_t* rows_b, int kb,
+                            const float* side_a, const float* side_b, int B, int mode, float alpha,
+                            float floor_a, float floor_b, float min_score, int k_out,
+                            float* out_score, int64_t* out_rows, float* out_a, float* out_b,
+                            int device, void* stream);
 
 /* Exact cosine of given (query, row) pairs on the fp16 rows (either scan dtype): out_sim[b, j] =
  * q_b . x_rows[b, j] with the query normalised as a search normalises it and fp32 accumulation;
@@ -411,10 +451,16 @@ int sr_store_score_rows_dev(sr_store* s, const void* q, int q_dtype, int B, cons
  * B x k (k in [1, 2 k_each], k_each in [1, SR_MAX_TOPK]); out_score fp32 fused scores, out_dense /
  * out_lex (optional) the components.  SR_FUSE_MINMAX passes no side scores.  SR_FUSE_FLOOR uses
  * floor_a = -1 (cosine), floor_b = 0 (BM25) and completes the dense side: side_a = the exact
- * cosines (sr_store_score_rows semantics) of the BM25 list's rows.  The BM25 side is NOT completed
- * for dense-only rows (the index keeps no per-row offsets into its forward postings): a row that
- * shares no term with the query has BM25 exactly 0, which is the floor, so only a row that matches
- * but was truncated from the BM25 top-k_each is under-scored, by less than that list's minimum. */
+ * cosines (sr_store_score_rows semantics) of the BM25 list's rows.  In SR_FUSE_FLOOR the BM25 side
+ * is NOT completed for dense-only rows: a row that shares no term with the query has BM25 exactly
+ * 0, which is the floor, so only a row that matches but was truncated from the BM25 top-k_each is
+ * under-scored, by less than that list's minimum.  SR_FUSE_FLOOR_FULL completes that side too: it is
+ * SR_FUSE_FLOOR plus side_b = the exact BM25 (sr_lex_score_rows semantics, this index's statistics)
+ * of the dense list's rows, with a score of exactly 0 passed as -inf (unknown).  A non-matching row
+ * then scores as in SR_FUSE_FLOOR (unknown -> 0) and not by the fusion's "known score on an empty
+ * list -> 1" rule, which would add 1 - alpha to every row when no row matches the query; only
+ * matching rows truncated from the BM25 list change, and a row's fused score no longer depends on
+ * where k_each cut the other list. */
 int sr_hybrid_search_fused(sr_store* s, sr_lex* x, const float* q, const int64_t* qoff,
                            const int32_t* qterms, int B, int k, int k_each, int mode, float alpha,
                            float min_score, const uint8_t* allow, int64_t mask_key,

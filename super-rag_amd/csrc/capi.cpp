@@ -1,6 +1,7 @@
 // C-ABI entry points (include/super_rag_mi355x.h): argument checks, exception -> error-code
 // mapping, per-object locking, and the HIP-event profiler.
 #include <algorithm>
+#include <cmath>
 #include <map>
 #include <mutex>
 #include <vector>
@@ -668,6 +669,37 @@ int sr_lex_search_tok_dev(sr_lex* x, const int32_t* tok, const int32_t* qlen, in
   SR_API_END
 }
 
+int sr_lex_score_rows(sr_lex* x, const int64_t* qoff, const int32_t* qterms, int B,
+                      const int64_t* rows, int K, const sr_lex_global* global, float* out_score,
+                      uint32_t* out_fixed) {
+  SR_API_BEGIN
+  SR_CHECK(B >= 0 && K >= 0, "lex.score_rows: negative shape");
+  SR_NONNULL(x);
+  if (B == 0 || K == 0) return SR_OK;
+  SR_NONNULL(qoff);
+  SR_NONNULL(rows);
+  SR_NONNULL(out_score);
+  std::lock_guard<std::mutex> lk(x->impl->mu);
+  x->impl->score_rows_host(qoff, qterms, B, rows, K, global, out_score, out_fixed);
+  SR_API_END
+}
+
+int sr_lex_score_rows_dev(sr_lex* x, const int64_t* qoff, const int32_t* qterms, int B,
+                          const int64_t* rows, int K, const sr_lex_global* global,
+                          int64_t row_offset, float* out_score, uint32_t* out_fixed, void* stream) {
+  SR_API_BEGIN
+  SR_CHECK(B >= 0 && K >= 0, "lex.score_rows: negative shape");
+  SR_NONNULL(x);
+  if (B == 0 || K == 0) return SR_OK;
+  SR_NONNULL(qoff);
+  SR_NONNULL(rows);
+  SR_NONNULL(out_score);
+  std::lock_guard<std::mutex> lk(x->impl->mu);
+  x->impl->score_rows_dev(qoff, qterms, B, rows, K, global, row_offset, out_score, out_fixed,
+                          reinterpret_cast<hipStream_t>(stream));
+  SR_API_END
+}
+
 int sr_lex_save(sr_lex* x, const char* path) {
   SR_API_BEGIN
   SR_NONNULL(x);
@@ -809,10 +841,11 @@ static void fuse_check_buffers(const float* score_a, const int64_t* rows_a, int 
   SR_CHECK(kb == 0 || (score_b && rows_b), "score_fuse: null list b");
 }
 
-int sr_score_fuse(const float* score_a, const int64_t* rows_a, int ka, const float* score_b,
-                  const int64_t* rows_b, int kb, const float* side_a, int B, int mode, float alpha,
-                  float floor_a, float floor_b, float min_score, int k_out, float* out_score,
-                  int64_t* out_rows, float* out_a, float* out_b, int device) {
+int sr_score_fuse_sides(const float* score_a, const int64_t* rows_a, int ka, const float* score_b,
+                        const int64_t* rows_b, int kb, const float* side_a, const float* side_b,
+                        int B, int mode, float alpha, float floor_a, float floor_b, float min_score,
+                        int k_out, float* out_score, int64_t* out_rows, float* out_a, float* out_b,
+                        int device) {
   SR_API_BEGIN
   sr::fuse_check_args(B, ka, kb, mode, alpha, k_out);
   if (B == 0) return SR_OK;
@@ -822,10 +855,11 @@ int sr_score_fuse(const float* score_a, const int64_t* rows_a, int ka, const flo
   for (int64_t i = 0; i < (int64_t)B * kb; ++i)
     SR_CHECK(rows_b[i] <= 0xfffffffeLL, "score_fuse: rows must be in [0, 2^32 - 2] (or < 0: absent)");
   sr::DeviceGuard g(device);
-  // staging: rows a | rows b | out rows | score a | score b | side a | out score | out a | out b
+  // staging: rows a | rows b | out rows | score a | score b | side a | out score | out a | out b |
+  // side b
   const size_t na = (size_t)B * ka, nb = (size_t)B * kb, no = (size_t)B * k_out;
   sr::DevBuf ws;
-  ws.reserve((na + nb + no) * 8 + (na + 2 * nb + 3 * no) * 4 + 8);
+  ws.reserve((na + nb + no) * 8 + (2 * na + 2 * nb + 3 * no) * 4 + 8);
   int64_t* da_r = ws.as<int64_t>();
   int64_t* db_r = da_r + na;
   int64_t* do_r = db_r + nb;
@@ -835,12 +869,14 @@ int sr_score_fuse(const float* score_a, const int64_t* rows_a, int ka, const flo
   float* do_s = dside + nb;
   float* do_a = do_s + no;
   float* do_b = do_a + no;
+  float* dsideb = do_b + no;
   hipStream_t st = nullptr;
   SR_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
   try {
     if (na) {
       SR_HIP(hipMemcpyAsync(da_r, rows_a, na * 8, hipMemcpyHostToDevice, st));
       SR_HIP(hipMemcpyAsync(da_s, score_a, na * 4, hipMemcpyHostToDevice, st));
+      if (side_b) SR_HIP(hipMemcpyAsync(dsideb, side_b, na * 4, hipMemcpyHostToDevice, st));
     }
     if (nb) {
       SR_HIP(hipMemcpyAsync(db_r, rows_b, nb * 8, hipMemcpyHostToDevice, st));
@@ -849,7 +885,7 @@ int sr_score_fuse(const float* score_a, const int64_t* rows_a, int ka, const flo
     }
     sr::launch_score_fuse(da_s, da_r, ka, db_s, db_r, kb, side_a ? dside : nullptr, B, mode, alpha,
                           floor_a, floor_b, min_score, k_out, do_s, do_r, out_a ? do_a : nullptr,
-                          out_b ? do_b : nullptr, st);
+                          out_b ? do_b : nullptr, st, side_b ? dsideb : nullptr);
     SR_HIP(hipMemcpyAsync(out_score, do_s, no * 4, hipMemcpyDeviceToHost, st));
     SR_HIP(hipMemcpyAsync(out_rows, do_r, no * 8, hipMemcpyDeviceToHost, st));
     if (out_a) SR_HIP(hipMemcpyAsync(out_a, do_a, no * 4, hipMemcpyDeviceToHost, st));
@@ -864,11 +900,21 @@ int sr_score_fuse(const float* score_a, const int64_t* rows_a, int ka, const flo
   SR_API_END
 }
 
-int sr_score_fuse_dev(const float* score_a, const int64_t* rows_a, int ka, const float* score_b,
-                      const int64_t* rows_b, int kb, const float* side_a, int B, int mode,
-                      float alpha, float floor_a, float floor_b, float min_score, int k_out,
-                      float* out_score, int64_t* out_rows, float* out_a, float* out_b, int device,
-                      void* stream) {
+int sr_score_fuse(const float* score_a, const int64_t* rows_a, int ka, const float* score_b,
+                  const int64_t* rows_b, int kb, const float* side_a, int B, int mode, float alpha,
+                  float floor_a, float floor_b, float min_score, int k_out, float* out_score,
+                  int64_t* out_rows, float* out_a, float* out_b, int device) {
+  return sr_score_fuse_sides(score_a, rows_a, ka, score_b, rows_b, kb, side_a, nullptr, B, mode, alpha,
+                             floor_a, floor_b, min_score, k_out, out_score, out_rows, out_a, out_b,
+                             device);
+}
+
+int sr_score_fuse_sides_dev(const float* score_a, const int64_t* rows_a, int ka,
+                            const float* score_b, const int64_t* rows_b, int kb,
+                            const float* side_a, const float* side_b, int B, int mode, float alpha,
+                            float floor_a, float floor_b, float min_score, int k_out,
+                            float* out_score, int64_t* out_rows, float* out_a, float* out_b,
+                            int device, void* stream) {
   SR_API_BEGIN
   sr::fuse_check_args(B, ka, kb, mode, alpha, k_out);
   if (B == 0) return SR_OK;
@@ -876,8 +922,18 @@ int sr_score_fuse_dev(const float* score_a, const int64_t* rows_a, int ka, const
   sr::DeviceGuard g(device);
   sr::launch_score_fuse(score_a, rows_a, ka, score_b, rows_b, kb, side_a, B, mode, alpha, floor_a,
                         floor_b, min_score, k_out, out_score, out_rows, out_a, out_b,
-                        reinterpret_cast<hipStream_t>(stream));
+                        reinterpret_cast<hipStream_t>(stream), side_b);
   SR_API_END
+}
+
+int sr_score_fuse_dev(const float* score_a, const int64_t* rows_a, int ka, const float* score_b,
+                      const int64_t* rows_b, int kb, const float* side_a, int B, int mode,
+                      float alpha, float floor_a, float floor_b, float min_score, int k_out,
+                      float* out_score, int64_t* out_rows, float* out_a, float* out_b, int device,
+                      void* stream) {
+  return sr_score_fuse_sides_dev(score_a, rows_a, ka, score_b, rows_b, kb, side_a, nullptr, B, mode,
+                                 alpha, floor_a, floor_b, min_score, k_out, out_score, out_rows, out_a,
+                                 out_b, device, stream);
 }
 
 int sr_store_score_rows(sr_store* s, const float* q, int B, const int64_t* rows, int K,
@@ -919,7 +975,7 @@ int sr_hybrid_search_fused(sr_store* s, sr_lex* x, const float* q, const int64_t
   SR_CHECK(B >= 0, "hybrid: negative batch");
   SR_CHECK(k_each >= 1 && k_each <= SR_MAX_TOPK, "hybrid: k_each must be in [1, 1024]");
   SR_CHECK(k >= 1 && k <= 2 * k_each, "hybrid: k must be in [1, 2 * k_each]");
-  sr::fuse_check_args(B, k_each, k_each, mode, alpha, k);
+  sr::fuse_check_args(B, k_each, k_each, mode, alpha, k, /*allow_full=*/true);
   SR_NONNULL(s);
   SR_NONNULL(x);
   if (B == 0) return SR_OK;
@@ -936,11 +992,12 @@ int sr_hybrid_search_fused(sr_store* s, sr_lex* x, const float* q, const int64_t
   SR_CHECK(lrows == st.rows(), "hybrid: store and lexical index hold different row counts");
   sr::DeviceGuard g(st.device());
   hipStream_t sm = lx.stream();
-  // staging: queries | dense rows | lex rows | out rows | dense sims | lex scores | side | out x 3
+  // staging: queries | dense rows | lex rows | out rows | dense sims | lex scores | side | out x 3 |
+  // side b
   const size_t bq = (size_t)sr::round_up((int64_t)B * st.dim() * 4, 16);
   const size_t ne = (size_t)B * k_each, no = (size_t)B * k;
   sr::DevBuf ws;
-  ws.reserve(bq + (2 * ne + no) * 8 + (3 * ne + 3 * no) * 4 + 64);
+  ws.reserve(bq + (2 * ne + no) * 8 + (4 * ne + 3 * no) * 4 + 64);
   char* w = ws.as<char>();
   float* dq = reinterpret_cast<float*>(w);
   int64_t* drow = reinterpret_cast<int64_t*>(w + bq);
@@ -952,16 +1009,20 @@ int sr_hybrid_search_fused(sr_store* s, sr_lex* x, const float* q, const int64_t
   float* os = side + ne;
   float* oa = os + no;
   float* ob = oa + no;
-  const bool floor_mode = mode == SR_FUSE_FLOOR;
+  float* sideb = ob + no;
+  const bool full = mode == SR_FUSE_FLOOR_FULL;
+  const bool floor_mode = mode == SR_FUSE_FLOOR || full;
   const uint8_t* elig = st.eligibility(allow, mask_key);
   lx.begin(sm);
   SR_HIP(hipMemcpyAsync(dq, q, (size_t)B * st.dim() * 4, hipMemcpyHostToDevice, sm));
   st.search_dev(dq, SR_DTYPE_F32, B, k_each, dsim, drow, 0, sm, elig);
   lx.search_dev(qoff, qterms, B, k_each, allow, mask_key, lsc, lrow, sm);
   if (floor_mode) st.score_rows_dev(dq, SR_DTYPE_F32, B, lrow, k_each, 0, side, sm);
-  sr::launch_score_fuse(dsim, drow, k_each, lsc, lrow, k_each, floor_mode ? side : nullptr, B, mode,
-                        alpha, -1.0f, 0.0f, min_score, k, os, orow, out_dense ? oa : nullptr,
-                        out_lex ? ob : nullptr, sm);
+  // the exact BM25 of the dense rows; a row that matches nothing (score 0) stays unknown
+  if (full) lx.score_rows_dev(qoff, qterms, B, drow, k_each, nullptr, 0, sideb, nullptr, sm, -INFINITY);
+  sr::launch_score_fuse(dsim, drow, k_each, lsc, lrow, k_each, floor_mode ? side : nullptr, B,
+                        full ? SR_FUSE_FLOOR : mode, alpha, -1.0f, 0.0f, min_score, k, os, orow,
+                        out_dense ? oa : nullptr, out_lex ? ob : nullptr, sm, full ? sideb : nullptr);
   SR_HIP(hipMemcpyAsync(out_score, os, no * 4, hipMemcpyDeviceToHost, sm));
   SR_HIP(hipMemcpyAsync(out_rows, orow, no * 8, hipMemcpyDeviceToHost, sm));
   if (out_dense) SR_HIP(hipMemcpyAsync(out_dense, oa, no * 4, hipMemcpyDeviceToHost, sm));

@@ -4,13 +4,14 @@
 //
 // score_fuse, one workgroup (8 waves) per query, fuses two scored row lists a [ka] and b [kb]
 // (row < 0: an absent entry, anywhere; a row at most once per list; no order assumed) with the
-// optional a-metric scores side_a [kb] of the b rows (include/super_rag_mi355x.h states the function):
+// optional a-metric scores side_a [kb] of the b rows and, its mirror, the optional b-metric scores
+// side_b [ka] of the a rows (include/super_rag_mi355x.h states the function):
 //   1. hi / lo of each list: block reduction over its valid scores (side scores never enter)
 //   2. slot -> join key (row + 1) << 13 | list << 12 | index, list a = 1, 0 for an absent entry;
 //      bitonic_sort_desc: the entries of one row are adjacent, list a's first
 //   3. the first entry of a row (its head) takes the row's a and b scores: the a entry's score or,
 //      for a row of list b alone, side_a; the b score from the entry itself or the one behind the
-//      head.  fused = alpha norm_a + (1 - alpha) norm_b, every operation rounded once (no contraction)
+//      head or, for a row of list a alone, side_b.  fused = alpha norm_a + (1 - alpha) norm_b, every operation rounded once (no contraction)
 //   4. the head's slot becomes ordered_bits(fused) << 32 | position + 1 (0: not a head, or below
 //      min_score) while src[position] keeps (index in a + 1) | (index in b + 1) << 12.  The join order
 //      is row DESCENDING, so on equal fused scores the larger position is the smaller row: the second
@@ -45,6 +46,7 @@ struct FuseArgs {
   const int64_t* rows_b;    // [B][kb]
   int kb;
   const float* side_a;      // [B][kb] or null
+  const float* side_b;      // [B][ka] or null
   int N;                    // power of two >= ka + kb, in [64, FMAXN]
   int mode;
   float alpha, one_minus_alpha, floor_a, floor_b, min_score;
@@ -80,6 +82,7 @@ __global__ __launch_bounds__(FTHREADS, 1) void score_fuse_kernel(FuseArgs a) {
   const float* sb = a.score_b + (int64_t)b * kb;
   const int64_t* rb = a.rows_b + (int64_t)b * kb;
   const float* side = a.side_a ? a.side_a + (int64_t)b * kb : nullptr;
+  const float* sideb = a.side_b ? a.side_b + (int64_t)b * ka : nullptr;
 
   // 1. + 2. join keys, and the extremes of each list's valid scores
   float hia = -INFINITY, loa = INFINITY, hib = -INFINITY, lob = INFINITY;
@@ -153,6 +156,7 @@ __global__ __launch_bounds__(FTHREADS, 1) void score_fuse_kernel(FuseArgs a) {
     if (ia >= 0) xa = sa[ia];
     else if (side) xa = side[ib];
     if (ib >= 0) xb = sb[ib];
+    else if (sideb) xb = sideb[ia];
     const float na = xa > -INFINITY ? fuse_norm(xa, hia, loa) : 0.f;
     const float nb = xb > -INFINITY ? fuse_norm(xb, hib, lob) : 0.f;
     const float fused = (a.alpha * na) + (a.one_minus_alpha * nb);
@@ -182,6 +186,7 @@ __global__ __launch_bounds__(FTHREADS, 1) void score_fuse_kernel(FuseArgs a) {
       if (ia >= 0) xa = sa[ia];
       else if (side) xa = side[ib];
       if (ib >= 0) xb = sb[ib];
+      else if (sideb) xb = sideb[ia];
     }
     a.out_score[ob + i] = fs;
     a.out_rows[ob + i] = row;
@@ -221,11 +226,11 @@ __global__ __launch_bounds__(RTHREADS) void score_rows_kernel(
 
 }  // namespace
 
-void fuse_check_args(int B, int ka, int kb, int mode, float alpha, int k_out) {
+void fuse_check_args(int B, int ka, int kb, int mode, float alpha, int k_out, bool allow_full) {
   SR_CHECK(B >= 0, "score_fuse: negative batch");
   SR_CHECK(ka >= 0 && ka <= FMAXL && kb >= 0 && kb <= FMAXL, "score_fuse: list length must be in [0, 2048]");
   SR_CHECK(k_out >= 1 && k_out <= FMAXL, "score_fuse: k_out must be in [1, 2048]");
-  SR_CHECK(mode == SR_FUSE_MINMAX || mode == SR_FUSE_FLOOR,
+  SR_CHECK(mode == SR_FUSE_MINMAX || mode == SR_FUSE_FLOOR || (allow_full && mode == SR_FUSE_FLOOR_FULL),
            "score_fuse: mode must be SR_FUSE_MINMAX or SR_FUSE_FLOOR");
   SR_CHECK(alpha >= 0.f && alpha <= 1.f, "score_fuse: alpha must be in [0, 1]");   // (false for NaN)
 }
@@ -234,7 +239,7 @@ void launch_score_fuse(const float* score_a, const int64_t* rows_a, int ka, cons
                        const int64_t* rows_b, int kb, const float* side_a, int B, int mode,
                        float alpha, float floor_a, float floor_b, float min_score, int k_out,
                        float* out_score, int64_t* out_rows, float* out_a, float* out_b,
-                       hipStream_t s) {
+                       hipStream_t s, const float* side_b) {
   fuse_check_args(B, ka, kb, mode, alpha, k_out);
   if (B == 0) return;
   int N = 64;
@@ -247,6 +252,7 @@ void launch_score_fuse(const float* score_a, const int64_t* rows_a, int ka, cons
   a.rows_b = rows_b;
   a.kb = kb;
   a.side_a = kb ? side_a : nullptr;
+  a.side_b = ka ? side_b : nullptr;
   a.N = N;
   a.mode = mode;
   a.alpha = alpha;
@@ -260,7 +266,7 @@ void launch_score_fuse(const float* score_a, const int64_t* rows_a, int ka, cons
   a.out_a = out_a;
   a.out_b = out_b;
   ProfScope prof("score_fuse", s, 0.0,
-                 (double)B * ((double)(ka + kb) * 12.0 + (side_a ? kb * 4.0 : 0.0) + k_out * 20.0));
+                 (double)B * ((double)(ka + kb) * 12.0 + (side_a ? kb * 4.0 : 0.0) + (side_b ? ka * 4.0 : 0.0) + k_out * 20.0));
   hipLaunchKernelGGL(score_fuse_kernel, dim3((unsigned)B), dim3(FTHREADS), 0, s, a);
   SR_LAUNCH_CHECK();
 }

@@ -7,6 +7,8 @@
 // Layout in HBM
 //   forward index (append-only, row order): fterm[P] int32, fval[P] u64 = row << 32 | tf;
 //   dlen[rows] int32 (document length in tokens), live[rows] u8;
+//   foff[rows + 1] int64: first forward posting of each row (extended by add, derived from fval by
+//   load / compact; not part of the snapshot): what lex_score_rows reads a row's postings through;
 //   inverted index (CSR by term over LIVE documents, rebuilt on the device when dirty):
 //   off[T + 1] int64, post[nnz] u64 = row << 32 | tf, rows ascending inside a term (stable radix
 //   sort of the row-ordered forward index by term id, dead rows keyed past the vocabulary; off by a
@@ -26,6 +28,10 @@
 //   L2 lex_select: one workgroup per query: exact top-k of the candidate keys: a score histogram
 //      pass, then a pass collecting the keys of the top bins into LDS for the block radix select
 //      (sr_topk.h).
+// Scoring of given (query, row) pairs:
+//   R1 lex_score_rows: one wave per pair walks the row's own forward postings through foff and sums
+//      the same fixed-point weights for the postings whose term is one of the query's scored terms
+//      (term table in LDS, binary search): the exact score the search gives that row.
 // Fusion:
 //   F1 rrf_fuse: one workgroup per query: rrf score of a row = sum over the lists of
 //      1 / (rank + rank_const) in fp64 (list a first, as graphiti accumulates), ordered by score
@@ -217,6 +223,88 @@ __global__ __launch_bounds__(LEX_THREADS) void lex_score_kernel(
       kl[__popcll(bal & ((1ull << lane) - 1ull))] = ((uint64_t)sc << 32) | (uint64_t)(0xffffffffu - row);
     }
     kl += __popcll(bal);
+  }
+}
+
+// ---- R1 lex_score_rows ------------------------------------------------------------------------------
+// Exact BM25 of given (query, row) pairs: one wave per pair, LSR_PAIRS pairs per workgroup, all of
+// one query b (blockIdx.y, strided past 65,535).  The query's term table (term ids ascending, idf,
+// multiplicity; LexIndex::score_rows_dev builds the terms search_dev scores) comes into LDS in
+// batches of LSR_TB; the lanes stride over the row's own forward postings [foff[r], foff[r + 1]) and
+// look each posting's term up in the batch (binary search), so a row that carries a term twice
+// sums both postings, as the search does.  Integer accumulation and an integer wave reduction: the
+// sum is the one lex_score_kernel's LDS atomics reach, bit for bit.  A row (minus row_offset)
+// outside [0, rows) or tombstoned is rejected before anything is indexed by it.
+constexpr int LSR_THREADS = 256;
+constexpr int LSR_PAIRS = LSR_THREADS / 64;
+constexpr int LSR_TB = 64;   // terms per LDS batch
+
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(LSR_THREADS) void lex_score_rows_kernel(
+    const int32_t* __restrict__ fterm, const uint64_t* __restrict__ fval,
+    const int64_t* __restrict__ foff, int64_t P, const int32_t* __restrict__ dlen,
+    const uint8_t* __restrict__ live, int64_t n_rows, const int* __restrict__ qt_off,
+    const int32_t* __restrict__ qt_term, const float* __restrict__ qt_idf,
+    const int32_t* __restrict__ qt_mult, const int64_t* __restrict__ rows, int B, int K,
+    int64_t row_offset, float avgdl, float k1, float b, float miss, float* __restrict__ out_score,
+    uint32_t* __restrict__ out_fixed) {
+  __shared__ int32_t s_term[LSR_TB];
+  __shared__ float s_idf[LSR_TB];
+  __shared__ int32_t s_mult[LSR_TB];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int j = blockIdx.x * LSR_PAIRS + (tid >> 6);
+  const float one_minus_b = 1.f - b, k1p1 = k1 + 1.f;
+  for (int q = blockIdx.y; q < B; q += gridDim.y) {   // (uniform over the workgroup)
+    bool ok = false;
+    int64_t p0 = 0, p1 = 0;
+    float dl = 0.f;
+    if (j < K) {   // (wave-uniform)
+      const int64_t raw = rows[(int64_t)q * K + j];
+      const int64_t r = raw - row_offset;
+      ok = raw >= 0 && r >= 0 && r < n_rows && live[r] != 0;
+      if (ok) {
+        p0 = foff[r];
+        p1 = foff[r + 1];
+        p1 = p1 < P ? p1 : P;
+        dl = (float)dlen[r];
+      }
+    }
+    uint32_t acc = 0u;
+    const int t0 = qt_off[q], t1 = qt_off[q + 1];
+    for (int tb = t0; tb < t1; tb += LSR_TB) {
+      const int nt = t1 - tb < LSR_TB ? t1 - tb : LSR_TB;
+      __syncthreads();   // previous batch (or query) done with s_*
+      if (tid < nt) {
+        s_term[tid] = qt_term[tb + tid];
+        s_idf[tid] = qt_idf[tb + tid];
+        s_mult[tid] = qt_mult[tb + tid];
+      }
+      __syncthreads();
+      for (int64_t p = p0 + lane; p < p1; p += 64) {
+        const int32_t t = fterm[p];
+        int lo = 0, hi = nt;   // first slot with term >= t
+        while (lo < hi) {
+          const int mid = (lo + hi) >> 1;
+          if (s_term[mid] < t) lo = mid + 1;
+          else hi = mid;
+        }
+        if (lo < nt && s_term[lo] == t) {
+          const float tf = (float)(uint32_t)fval[p];
+          acc += bm25_fixed(s_idf[lo], tf, dl, avgdl, k1, b, one_minus_b, k1p1) * (uint32_t)s_mult[lo];
+        }
+      }
+    }
+    acc = wave_sum_u32(acc);
+    if (lane == 0 && j < K) {
+      const int64_t o = (int64_t)q * K + j;
+      out_score[o] = !ok ? -INFINITY : (acc ? (float)acc / LEX_SCALE : miss);
+      if (out_fixed) out_fixed[o] = acc;
+    }
   }
 }
 
@@ -568,6 +656,11 @@ void LexIndex::add(const int64_t* off, const int32_t* terms, const int32_t* tf, 
   grow_copy(fval_, (size_t)P_ * 8, (size_t)(P_ + P) * 8, stream_);
   grow_copy(dlen_, (size_t)rows_ * 4, (size_t)(rows_ + n) * 4, stream_);
   grow_copy(live_, (size_t)rows_, (size_t)(rows_ + n), stream_);
+  // foff[rows_ .. rows_ + n] = P_ + off[0 .. n] (entry rows_ = P_ is rewritten with the same value)
+  std::vector<int64_t> fo((size_t)n + 1);
+  for (int64_t i = 0; i <= n; ++i) fo[(size_t)i] = P_ + off[i];
+  grow_copy(foff_, foff_.p ? (size_t)(rows_ + 1) * 8 : 0, (size_t)(rows_ + n + 1) * 8, stream_);
+  SR_HIP(hipMemcpyAsync(foff_.as<int64_t>() + rows_, fo.data(), fo.size() * 8, hipMemcpyHostToDevice, stream_));
   if (P) {
     SR_HIP(hipMemcpyAsync(fterm_.as<int32_t>() + P_, terms, (size_t)P * 4, hipMemcpyHostToDevice, stream_));
     SR_HIP(hipMemcpyAsync(fval_.as<uint64_t>() + P_, val.data(), (size_t)P * 8, hipMemcpyHostToDevice, stream_));
@@ -702,6 +795,58 @@ void LexIndex::df(const int32_t* terms, int n, int64_t* out) {
   }
 }
 
+// ---- host-side query preparation shared by search_dev and score_rows_dev -------------------------
+namespace {
+
+struct LexQT {
+  int32_t term, mult;
+};
+
+// The terms of one query that are scored: distinct ids in [0, vocab) with live df > 0, in
+// first-occurrence order, mult = occurrences in the query.
+std::vector<LexQT> lex_query_terms(const int32_t* qterms, int64_t p0, int64_t p1, int64_t vocab,
+                                   const std::vector<int32_t>& df_host) {
+  std::vector<LexQT> v;
+  for (int64_t p = p0; p < p1; ++p) {
+    const int32_t t = qterms[p];
+    if (t < 0 || t >= vocab || df_host[(size_t)t] == 0) continue;
+    bool seen = false;
+    for (auto& e : v)
+      if (e.term == t) {
+        ++e.mult;
+        seen = true;
+      }
+    if (!seen) v.push_back({t, 1});
+  }
+  return v;
+}
+
+// N, summed length and df the idf and avgdl come from: the index's own, or the caller's table.
+struct LexStatsHost {
+  int64_t n_live, sum_dl;
+  bool global;
+  std::vector<std::pair<int32_t, int64_t>> gdf;
+  LexStatsHost(const sr_lex_global* glob, int64_t own_live, int64_t own_sum_dl)
+      : n_live(own_live), sum_dl(own_sum_dl), global(glob != nullptr) {
+    if (!glob) return;
+    SR_CHECK(glob->n_live >= 0 && glob->sum_dl >= 0 && (glob->n_terms == 0 || (glob->terms && glob->df)),
+             "lex.search: invalid global statistics");
+    n_live = glob->n_live;
+    sum_dl = glob->sum_dl;
+    gdf.reserve((size_t)glob->n_terms);
+    for (int i = 0; i < glob->n_terms; ++i) gdf.push_back({glob->terms[i], glob->df[i]});
+    std::sort(gdf.begin(), gdf.end());
+  }
+  int64_t df(int32_t t, const std::vector<int32_t>& df_host) const {
+    if (!global) return df_host[(size_t)t];
+    auto it = std::lower_bound(gdf.begin(), gdf.end(), std::make_pair(t, (int64_t)INT64_MIN));
+    SR_CHECK(it != gdf.end() && it->first == t, "lex.search: query term missing from the global df table");
+    return it->second;
+  }
+};
+
+}  // namespace
+
 void LexIndex::search_dev(const int64_t* qoff, const int32_t* qterms, int B, int k,
                           const uint8_t* allow, int64_t mask_key, float* out_score,
                           int64_t* out_rows, hipStream_t s, const sr_lex_global* glob,
@@ -715,49 +860,19 @@ void LexIndex::search_dev(const int64_t* qoff, const int32_t* qterms, int B, int
   rebuild(s);
   const uint8_t* elig = eligibility(allow, mask_key, s);
   // per query: distinct known terms with multiplicity, and the touched-list capacity
-  struct QT {
-    int32_t term, mult;
-  };
-  std::vector<std::vector<QT>> qt((size_t)B);
+  std::vector<std::vector<LexQT>> qt((size_t)B);
   std::vector<int64_t> cap((size_t)B, 0);
   for (int b = 0; b < B; ++b) {
     SR_CHECK(qoff[b + 1] >= qoff[b], "lex.search: qoff must be non-decreasing");
-    std::vector<QT>& v = qt[(size_t)b];
-    for (int64_t p = qoff[b]; p < qoff[b + 1]; ++p) {
-      const int32_t t = qterms[p];
-      if (t < 0 || t >= vocab_ || df_host_[(size_t)t] == 0) continue;
-      bool seen = false;
-      for (auto& e : v)
-        if (e.term == t) {
-          ++e.mult;
-          seen = true;
-        }
-      if (!seen) {
-        v.push_back({t, 1});
-        cap[(size_t)b] += df_host_[(size_t)t];
-      }
-    }
+    qt[(size_t)b] = lex_query_terms(qterms, qoff[b], qoff[b + 1], vocab_, df_host_);
+    for (const LexQT& e : qt[(size_t)b]) cap[(size_t)b] += df_host_[(size_t)e.term];
     cap[(size_t)b] = std::min<int64_t>(cap[(size_t)b], rows_);
   }
   // statistics: this index's live rows, or the caller's corpus-wide ones (row-sharded corpus:
   // every shard then scores with the same N, avgdl and df, so merged results equal one index's)
-  int64_t N_live = live_n_, sum_dl = sum_dl_;
-  std::vector<std::pair<int32_t, int64_t>> gdf;
-  if (glob) {
-    SR_CHECK(glob->n_live >= 0 && glob->sum_dl >= 0 && (glob->n_terms == 0 || (glob->terms && glob->df)),
-             "lex.search: invalid global statistics");
-    N_live = glob->n_live;
-    sum_dl = glob->sum_dl;
-    gdf.reserve((size_t)glob->n_terms);
-    for (int i = 0; i < glob->n_terms; ++i) gdf.push_back({glob->terms[i], glob->df[i]});
-    std::sort(gdf.begin(), gdf.end());
-  }
-  auto term_df = [&](int32_t t) -> int64_t {
-    if (!glob) return df_host_[(size_t)t];
-    auto it = std::lower_bound(gdf.begin(), gdf.end(), std::make_pair(t, (int64_t)INT64_MIN));
-    SR_CHECK(it != gdf.end() && it->first == t, "lex.search: query term missing from the global df table");
-    return it->second;
-  };
+  const LexStatsHost stats(glob, live_n_, sum_dl_);
+  const int64_t N_live = stats.n_live, sum_dl = stats.sum_dl;
+  auto term_df = [&](int32_t t) -> int64_t { return stats.df(t, df_host_); };
   // query blocks: candidate keys within LEX_KEY_BUDGET; grid (queries, row blocks), so the
   // workgroups in flight belong to many queries
   const int64_t rows = std::max<int64_t>(rows_, 1);
@@ -783,7 +898,7 @@ void LexIndex::search_dev(const int64_t* qoff, const int32_t* qterms, int B, int
     int64_t scored = 0;
     for (int i = 0; i < qb; ++i) {
       koff[(size_t)i + 1] = koff[(size_t)i] + cap[(size_t)(b0 + i)];
-      for (const QT& e : qt[(size_t)(b0 + i)]) {
+      for (const LexQT& e : qt[(size_t)(b0 + i)]) {
         const int64_t len = df_host_[(size_t)e.term];
         slots.push_back({off_host_[(size_t)e.term], (int32_t)len, idf(term_df(e.term), N_live), e.mult, 0});
         scored += len;
@@ -982,6 +1097,92 @@ void LexIndex::search_host(const int64_t* qoff, const int32_t* qterms, int B, in
   SR_HIP(hipStreamSynchronize(stream_));
 }
 
+// Exact BM25 of (query, row) pairs: the term tables of search_dev (same terms, idf and statistics),
+// sorted by term id for the kernel's binary search, then one lex_score_rows launch.
+void LexIndex::score_rows_dev(const int64_t* qoff, const int32_t* qterms, int B, const int64_t* rows,
+                              int K, const sr_lex_global* glob, int64_t row_offset, float* out_score,
+                              uint32_t* out_fixed, hipStream_t s, float miss) {
+  SR_CHECK(B >= 0 && K >= 0, "lex.score_rows: negative shape");
+  if (B == 0 || K == 0) return;
+  SR_CHECK(qoff && rows && out_score, "lex.score_rows: null buffer");
+  SR_CHECK(qoff[0] == 0, "lex.score_rows: qoff[0] must be 0");
+  for (int b = 0; b < B; ++b) SR_CHECK(qoff[b + 1] >= qoff[b], "lex.score_rows: qoff must be non-decreasing");
+  SR_CHECK(qoff[B] == 0 || qterms, "lex.score_rows: null query terms");
+  DeviceGuard g(device_);
+  begin(s);
+  rebuild(s);   // df_host_ (which terms are scored, and the idf) comes from the inverted index
+  const LexStatsHost stats(glob, live_n_, sum_dl_);
+  std::vector<int> qt_off((size_t)B + 1, 0);
+  std::vector<int32_t> term, mult;
+  std::vector<float> idfv;
+  for (int b = 0; b < B; ++b) {
+    std::vector<LexQT> v = lex_query_terms(qterms, qoff[b], qoff[b + 1], vocab_, df_host_);
+    std::sort(v.begin(), v.end(), [](const LexQT& x, const LexQT& y) { return x.term < y.term; });
+    for (const LexQT& e : v) {
+      term.push_back(e.term);
+      mult.push_back(e.mult);
+      idfv.push_back(idf(stats.df(e.term, df_host_), stats.n_live));
+    }
+    SR_CHECK(term.size() <= (size_t)0x7fffffff, "lex.score_rows: more than 2^31 query terms");
+    qt_off[(size_t)b + 1] = (int)term.size();
+  }
+  const size_t nt = term.size();
+  size_t o = 0;
+  auto carve = [&](size_t bytes) {
+    const size_t at = o;
+    o += (size_t)round_up((int64_t)std::max<size_t>(bytes, 1), 256);
+    return at;
+  };
+  const size_t o_off = carve(qt_off.size() * 4), o_t = carve(nt * 4), o_i = carve(nt * 4), o_m = carve(nt * 4);
+  ws_.reserve(o);
+  char* w = ws_.as<char>();
+  int* d_off = reinterpret_cast<int*>(w + o_off);
+  int32_t* d_t = reinterpret_cast<int32_t*>(w + o_t);
+  float* d_i = reinterpret_cast<float*>(w + o_i);
+  int32_t* d_m = reinterpret_cast<int32_t*>(w + o_m);
+  SR_HIP(hipMemcpyAsync(d_off, qt_off.data(), qt_off.size() * 4, hipMemcpyHostToDevice, s));
+  if (nt) {
+    SR_HIP(hipMemcpyAsync(d_t, term.data(), nt * 4, hipMemcpyHostToDevice, s));
+    SR_HIP(hipMemcpyAsync(d_i, idfv.data(), nt * 4, hipMemcpyHostToDevice, s));
+    SR_HIP(hipMemcpyAsync(d_m, mult.data(), nt * 4, hipMemcpyHostToDevice, s));
+  }
+  {
+    // expected traffic at the index's mean postings per row (the host keeps no per-row counts):
+    // row id, two offsets, length, live flag and the two outputs per pair, 12 B per posting
+    const double per_row = rows_ > 0 ? (double)P_ / (double)rows_ : 0.0;
+    ProfScope prof("lex_score_rows", s, 0.0, (double)B * K * (37.0 + per_row * 12.0));
+    hipLaunchKernelGGL(lex_score_rows_kernel, dim3((unsigned)ceil_div(K, LSR_PAIRS), (unsigned)std::min(B, 65535)),
+                       dim3(LSR_THREADS), 0, s, fterm_.as<int32_t>(), fval_.as<uint64_t>(),
+                       foff_.as<int64_t>(), P_, dlen_.as<int32_t>(), live_.as<uint8_t>(), rows_, d_off,
+                       d_t, d_i, d_m, rows, B, K, row_offset, avgdl(stats.sum_dl, stats.n_live), k1_, b_,
+                       miss, out_score, out_fixed);
+    SR_LAUNCH_CHECK();
+  }
+  // the host vectors above back async copies: finish before they go away
+  SR_HIP(hipStreamSynchronize(s));
+  end(s);
+}
+
+void LexIndex::score_rows_host(const int64_t* qoff, const int32_t* qterms, int B, const int64_t* rows,
+                               int K, const sr_lex_global* glob, float* out_score, uint32_t* out_fixed) {
+  SR_CHECK(B >= 0 && K >= 0, "lex.score_rows: negative shape");
+  if (B == 0 || K == 0) return;
+  SR_CHECK(rows && out_score, "lex.score_rows: null buffer");
+  DeviceGuard g(device_);
+  const size_t n = (size_t)B * K;
+  out_.reserve(n * 16);   // rows | score | fixed
+  int64_t* dr = out_.as<int64_t>();
+  float* ds = reinterpret_cast<float*>(dr + n);
+  uint32_t* dfx = reinterpret_cast<uint32_t*>(ds + n);
+  begin(stream_);
+  SR_HIP(hipMemcpyAsync(dr, rows, n * 8, hipMemcpyHostToDevice, stream_));
+  end(stream_);
+  score_rows_dev(qoff, qterms, B, dr, K, glob, 0, ds, out_fixed ? dfx : nullptr, stream_);
+  SR_HIP(hipMemcpyAsync(out_score, ds, n * 4, hipMemcpyDeviceToHost, stream_));
+  if (out_fixed) SR_HIP(hipMemcpyAsync(out_fixed, dfx, n * 4, hipMemcpyDeviceToHost, stream_));
+  SR_HIP(hipStreamSynchronize(stream_));
+}
+
 void LexIndex::stats(int64_t* rows, int64_t* live, int64_t* postings, int64_t* vocab,
                      double* avgdl_out) {
   if (rows) *rows = rows_;
@@ -1086,6 +1287,14 @@ LexIndex* LexIndex::load(const char* path, int device) {
 void LexIndex::load_rows(const std::vector<int32_t>& dl, const std::vector<uint8_t>& live,
                          const std::vector<int32_t>& ft, const std::vector<uint64_t>& fv) {
   const int64_t rows = (int64_t)dl.size(), P = (int64_t)ft.size();
+  // foff[r] = postings of the rows before r (fv is row-ordered: load validates it, compact keeps it)
+  std::vector<int64_t> fo((size_t)rows + 1, 0);
+  for (int64_t p = 0; p < P; ++p) {
+    const int64_t r = (int64_t)(fv[(size_t)p] >> 32);
+    SR_CHECK(r < rows, "lex: posting of a row past the index");
+    ++fo[(size_t)r + 1];
+  }
+  for (int64_t r = 0; r < rows; ++r) fo[(size_t)r + 1] += fo[(size_t)r];
   DeviceGuard g(device_);
   begin(stream_);
   SR_HIP(hipStreamSynchronize(stream_));
@@ -1097,6 +1306,9 @@ void LexIndex::load_rows(const std::vector<int32_t>& dl, const std::vector<uint8
   fval_.reserve((size_t)std::max<int64_t>(P, 1) * 8);
   dlen_.reserve((size_t)std::max<int64_t>(rows, 1) * 4);
   live_.reserve((size_t)std::max<int64_t>(rows, 1));
+  foff_.release();
+  foff_.reserve(fo.size() * 8);
+  SR_HIP(hipMemcpyAsync(foff_.p, fo.data(), fo.size() * 8, hipMemcpyHostToDevice, stream_));
   if (P) {
     SR_HIP(hipMemcpyAsync(fterm_.p, ft.data(), (size_t)P * 4, hipMemcpyHostToDevice, stream_));
     SR_HIP(hipMemcpyAsync(fval_.p, fv.data(), (size_t)P * 8, hipMemcpyHostToDevice, stream_));

@@ -248,17 +248,17 @@ void launch_group_mask(const uint8_t* base, const int32_t* group, int64_t n_rows
 
 // k_fuse.hip — score fusion of two scored row lists per query (one workgroup each; the function is
 // stated in include/super_rag_mi355x.h): lists (score, rows) of ka / kb entries, row < 0 absent,
-// side_a [B][kb] optional a-scores of the b rows; outputs B x k_out by (fused desc, row asc),
+// side_a [B][kb] optional a-scores of the b rows, side_b [B][ka] optional b-scores of the a rows; outputs B x k_out by (fused desc, row asc),
 // -inf / -1 unfilled, out_a / out_b optional components.  fuse_check_args throws SR_ERR_INVALID
-// outside the documented limits.  launch_score_rows: out[b][j] = qn_b . row (rows[b][j] - row_offset)
+// outside the documented limits (allow_full: SR_FUSE_FLOOR_FULL passes, for sr_hybrid_search_fused).  launch_score_rows: out[b][j] = qn_b . row (rows[b][j] - row_offset)
 // over the fp16 rows (qn [B][ld] normalised, zero padded), -inf for a row outside [0, n_rows) or with
 // live == 0; one wave per pair.
-void fuse_check_args(int B, int ka, int kb, int mode, float alpha, int k_out);
+void fuse_check_args(int B, int ka, int kb, int mode, float alpha, int k_out, bool allow_full = false);
 void launch_score_fuse(const float* score_a, const int64_t* rows_a, int ka, const float* score_b,
                        const int64_t* rows_b, int kb, const float* side_a, int B, int mode,
                        float alpha, float floor_a, float floor_b, float min_score, int k_out,
                        float* out_score, int64_t* out_rows, float* out_a, float* out_b,
-                       hipStream_t s);
+                       hipStream_t s, const float* side_b = nullptr);
 void launch_score_rows(const half_t* corpus, int ld, int64_t n_rows, const uint8_t* live,
                        const half_t* qn, const int64_t* rows, int B, int K, int64_t row_offset,
                        float* out, hipStream_t s);

@@ -306,6 +306,15 @@ class LexIndex {
   void search_host(const int64_t* qoff, const int32_t* qterms, int B, int k, const uint8_t* allow,
                    int64_t mask_key, float* out_score, int64_t* out_rows,
                    const sr_lex_global* glob = nullptr, uint32_t* out_fixed = nullptr);
+  // exact BM25 of given (query, row) pairs (k_lex.hip lex_score_rows): rows [B][K] on the device
+  // carry row_offset; out_score fp32 / out_fixed u32 (may be null) [B][K] on the device.  -inf / 0
+  // for a row outside [0, rows) or tombstoned, `miss` / 0 for a live row without a scored term.
+  // Synchronises s once (the host-built term tables).
+  void score_rows_dev(const int64_t* qoff, const int32_t* qterms, int B, const int64_t* rows, int K,
+                      const sr_lex_global* glob, int64_t row_offset, float* out_score,
+                      uint32_t* out_fixed, hipStream_t s, float miss = 0.f);
+  void score_rows_host(const int64_t* qoff, const int32_t* qterms, int B, const int64_t* rows, int K,
+                       const sr_lex_global* glob, float* out_score, uint32_t* out_fixed);
   void stats(int64_t* rows, int64_t* live, int64_t* postings, int64_t* vocab, double* avgdl);
   void save(const char* path);
   static LexIndex* load(const char* path, int device);
@@ -331,8 +340,9 @@ class LexIndex {
   hipEvent_t done_ = nullptr;
   int64_t rows_ = 0, live_n_ = 0, P_ = 0, vocab_ = 0, nnz_ = 0, sum_dl_ = 0, max_df_ = 0;
   bool dirty_ = true;
-  // device: forward index, per-row data, inverted index, workspaces
-  DevBuf fterm_, fval_, dlen_, live_, off_, post_, ws_, out_, mask_, caps_;
+  // device: forward index, per-row data (foff_[rows + 1]: first forward posting of each row),
+  // inverted index, workspaces
+  DevBuf fterm_, fval_, dlen_, live_, foff_, off_, post_, ws_, out_, mask_, caps_;
   // host mirrors
   std::vector<int32_t> dl_host_, df_host_;
   std::vector<uint8_t> live_host_;

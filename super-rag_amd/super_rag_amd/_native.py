@@ -34,6 +34,7 @@ SR_MMR_MAX_CAND = 128
 SR_GROUP_MAX_SIZE = 8
 SR_FUSE_MINMAX = 0
 SR_FUSE_FLOOR = 1
+SR_FUSE_FLOOR_FULL = 2
 
 
 class NativeUnavailableError(RuntimeError):
@@ -172,6 +173,17 @@ SIGNATURES = {
     "sr_profile_read": (c_int, [POINTER(KernelStatC), c_int, P_I32]),
     "sr_lex_search_global_fixed": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
                                            c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sr_lex_score_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                  c_void_p, c_void_p]),
+    "sr_lex_score_rows_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                      c_int64, c_void_p, c_void_p, c_void_p]),
+    "sr_score_fuse_sides": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                                    c_void_p, c_int, c_int, c_float, c_float, c_float, c_float, c_int,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_int]),
+    "sr_score_fuse_sides_dev": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                        c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_float,
+                                        c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                        c_void_p]),
 }
 
 # The diagnostic surface (include/super_rag_mi355x_diag.h), exported by libsrmi_diag.so only:

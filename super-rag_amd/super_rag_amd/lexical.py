@@ -13,7 +13,10 @@ The reference declares the pieces but ships no backend: a ``fulltext_search`` no
   * ``rrf_fuse`` / ``hybrid_search``: reciprocal-rank fusion as graphiti's ``rrf``
     (graphiti_core/search/search_utils.py:1762-1778), on the device;
   * ``score_fuse`` / ``hybrid_search(fusion="relative" | "floor")``: score-based fusion (weighted
-    min-max or floor-normalised cosine + BM25, k_fuse.hip), opt-in next to rrf.
+    min-max or floor-normalised cosine + BM25, k_fuse.hip), opt-in next to rrf;
+  * ``NativeLexIndex.score_rows`` / ``ShardedLex.score_rows``: the exact BM25 of given (query, row)
+    pairs (lex_score_rows), and ``fusion="floor_full"``: floor fusion with the BM25 side completed
+    by it for the dense list's rows, as the dense side already is.
 There is no CPU fallback: every entry point needs the HIP library and a GPU.
 """
 from __future__ import annotations
@@ -97,6 +100,16 @@ class LexGlobalC(ctypes.Structure):
     """sr_lex_global: corpus-wide statistics of a row-sharded lexical corpus."""
     _fields_ = [("n_live", ctypes.c_int64), ("sum_dl", ctypes.c_int64), ("terms", ctypes.c_void_p),
                 ("df", ctypes.c_void_p), ("n_terms", ctypes.c_int)]
+
+
+def _global_c(global_stats):
+    """(n_live, sum_dl, terms, df) -> (sr_lex_global, the arrays it points into), or (None, None)."""
+    if global_stats is None:
+        return None, None
+    n_live, sum_dl, gt, gdf = global_stats
+    gt = np.ascontiguousarray(gt, dtype=np.int32)
+    gdf = np.ascontiguousarray(gdf, dtype=np.int64)
+    return LexGlobalC(int(n_live), int(sum_dl), gt.ctypes.data, gdf.ctypes.data, int(gt.size)), (gt, gdf)
 
 
 def _mask(allow, n_rows: int):
@@ -211,6 +224,47 @@ class NativeLexIndex:
                    None if a is None else N.ptr(a), int(mask_key), ctypes.byref(g), N.ptr(scores),
                    N.ptr(rows))
         return scores, rows
+
+    def score_rows(self, queries: Sequence[Sequence[int]], rows, global_stats=None,
+                   fixed: bool = False):
+        """Exact BM25 of given (query, row) pairs (sr_lex_score_rows): queries as for search, rows
+        [B, K] int64 -> score [B, K] fp32, the score search gives that row for that query: -inf for a
+        row < 0, past the index or tombstoned, 0 for a live row that shares no scored term.
+        global_stats as for search; fixed: also the exact 2^-16 fixed-point scores [B, K] uint32."""
+        Bq = len(queries)
+        r = np.ascontiguousarray(np.asarray(rows, dtype=np.int64))
+        if r.ndim != 2 or r.shape[0] != Bq:
+            raise ValueError(f"rows must be [{Bq}, K], got {r.shape}")
+        score = np.empty(r.shape, dtype=np.float32)
+        fx = np.zeros(r.shape, dtype=np.uint32) if fixed else None
+        if r.size:
+            qoff, qterms = query_arrays(queries)
+            g, _keep = _global_c(global_stats)
+            N.call("sr_lex_score_rows", self._h, N.ptr(qoff), N.ptr(qterms), Bq, N.ptr(r), r.shape[1],
+                   None if g is None else ctypes.byref(g), N.ptr(score), N.ptr(fx) if fixed else None)
+        return (score, fx) if fixed else score
+
+    def score_rows_dev(self, qoff, qterms, rows, global_stats=None, row_offset: int = 0,
+                       fixed: bool = False, stream=None):
+        """score_rows on device rows: qoff / qterms host arrays (query_arrays), rows [B, K] int64
+        torch tensor on this device carrying ``row_offset`` -> score [B, K] fp32 device tensor (and
+        the fixed-point scores as int32 bit patterns of the uint32 values with ``fixed``);
+        sr_lex_score_rows_dev, ``stream`` synchronised once."""
+        import torch
+        qoff = np.ascontiguousarray(qoff, dtype=np.int64)
+        qterms = np.ascontiguousarray(qterms, dtype=np.int32)
+        Bq = len(qoff) - 1
+        rows = rows.contiguous()
+        if not (rows.is_cuda and rows.dtype == torch.int64 and rows.dim() == 2 and rows.shape[0] == Bq):
+            raise ValueError(f"rows must be a CUDA int64 tensor [{Bq}, K]")
+        score = torch.empty(rows.shape, dtype=torch.float32, device=rows.device)
+        fx = torch.zeros(rows.shape, dtype=torch.int32, device=rows.device) if fixed else None
+        if rows.numel():
+            g, _keep = _global_c(global_stats)
+            N.call("sr_lex_score_rows_dev", self._h, N.ptr(qoff), N.ptr(qterms), Bq, N.ptr(rows),
+                   rows.shape[1], None if g is None else ctypes.byref(g), int(row_offset),
+                   N.ptr(score), N.ptr(fx) if fixed else None, N.stream_handle(stream))
+        return (score, fx) if fixed else score
 
     def totals(self):
         """(live rows, summed document length) of this index."""
@@ -412,6 +466,33 @@ class ShardedLex:
             out_r[b, : ok.sum()] = R[b][o][ok]
         return out_s, out_r
 
+    def score_rows(self, queries, rows, fixed: bool = False):
+        """NativeLexIndex.score_rows with global rows: every pair goes to the shard that owns its
+        row and is scored with the corpus-wide statistics (global_stats(queries)), so the result
+        equals one index's bit for bit; -inf for a row < 0 (a -1 padded list), outside the
+        collection or tombstoned."""
+        Bq = len(queries)
+        r = np.asarray(rows, dtype=np.int64)
+        if r.ndim != 2 or r.shape[0] != Bq:
+            raise ValueError(f"rows must be [{Bq}, K], got {r.shape}")
+        n = self._n()
+        _, owner_of, local_of = self._route(np.zeros(0, np.int64))
+        ok = (r >= 0) & (r < n)
+        safe = np.where(ok, r, 0)
+        owner = np.where(ok, owner_of[safe] if n else -1, -1)
+        out = np.full(r.shape, -np.inf, dtype=np.float32)
+        out_fx = np.zeros(r.shape, dtype=np.uint32)
+        st = self.global_stats(queries) if r.size else None
+        for s, sh in enumerate(self.shards):
+            mine = owner == s
+            if not mine.any():
+                continue
+            local = np.where(mine, local_of[safe] if n else -1, -1)
+            got, fx = sh.score_rows(queries, local, global_stats=st, fixed=True)
+            out[mine] = np.asarray(got, np.float32)[mine]
+            out_fx[mine] = np.asarray(fx, np.uint32)[mine]
+        return (out, out_fx) if fixed else out
+
     def hybrid(self, store, queries, query_terms, k: int, k_each: Optional[int] = None,
                rank_const: int = 1, min_score: float = float("-inf"), allow=None, mask_key: int = 0,
                fusion: str = "rrf", alpha: float = 0.5):
@@ -420,7 +501,8 @@ class ShardedLex:
         / "floor", by score (sr_hybrid_search_fused's steps).  Score fusion works on the MERGED
         lists: the dense side merges on similarities (ShardedStore.search_sim), the normalisation
         sees the collection's lists, never a shard's, and "floor" completes the dense side through
-        ShardedStore.score_rows, so the result equals a single-device collection's bit for bit."""
+        ShardedStore.score_rows ("floor_full" also the BM25 side, through score_rows of the merged
+        dense list), so the result equals a single-device collection's bit for bit."""
         mode = fusion_mode(fusion)
         k_each = int(k_each or k)
         if mode is None:
@@ -430,9 +512,11 @@ class ShardedLex:
         check_alpha(alpha)
         sims, dense = store.search_sim(queries, k_each, allow=allow, mask_key=mask_key)
         lsc, lex = self.search(query_terms, k_each, allow=allow, mask_key=mask_key)
-        side = store.score_rows(queries, lex) if mode == N.SR_FUSE_FLOOR else None
-        score, rows, _, _ = _fuse_rows(sims, dense, lsc, lex, side, mode, alpha, -1.0, 0.0,
-                                       min_score, k, self.devices[0])
+        full = mode == N.SR_FUSE_FLOOR_FULL
+        side = store.score_rows(queries, lex) if (mode == N.SR_FUSE_FLOOR or full) else None
+        side_b = unknown_where_zero(self.score_rows(query_terms, dense)) if full else None
+        score, rows, _, _ = _fuse_rows(sims, dense, lsc, lex, side, N.SR_FUSE_FLOOR if full else mode,
+                                       alpha, -1.0, 0.0, min_score, k, self.devices[0], side_b)
         return score, rows
 
     def save(self, path: str) -> None:
@@ -472,13 +556,22 @@ def _rrf_rows(rows_a, rows_b, k, rank_const, min_score, device):
 
 
 def _fuse_rows(score_a, rows_a, score_b, rows_b, side_a, mode, alpha, floor_a, floor_b, min_score, k,
-               device):
-    """score_fuse of two host lists on the device, or through the test seam."""
+               device, side_b=None):
+    """score_fuse of two host lists on the device, or through the test seam (which sees ``side_b``
+    as a keyword, and only when there is one: a seam of before side_b keeps working)."""
+    kw = {} if side_b is None else {"side_b": side_b}
     return _fuse_impl[0](score_a, rows_a, score_b, rows_b, side_a, mode, alpha, floor_a, floor_b,
-                         min_score, k, device)
+                         min_score, k, device, **kw)
 
 
-FUSIONS = ("rrf", "relative", "floor")
+def unknown_where_zero(score) -> np.ndarray:
+    """BM25 pair scores -> "floor_full"'s side_b: a score of exactly 0 (the row matches nothing)
+    becomes -inf, unknown, so that row fuses as it does in "floor"."""
+    s = np.asarray(score, dtype=np.float32)
+    return np.where(s == 0, np.float32(-np.inf), s).astype(np.float32)
+
+
+FUSIONS = ("rrf", "relative", "floor", "floor_full")
 
 
 def fusion_mode(fusion: str):
@@ -489,6 +582,8 @@ def fusion_mode(fusion: str):
         return N.SR_FUSE_MINMAX
     if fusion == "floor":
         return N.SR_FUSE_FLOOR
+    if fusion == "floor_full":
+        return N.SR_FUSE_FLOOR_FULL
     raise ValueError(f"unsupported fusion '{fusion}' (one of {', '.join(FUSIONS)})")
 
 
@@ -536,17 +631,24 @@ def rrf_fuse_dev(rows_a, rows_b, k: int, rank_const: int = 1, min_score: float =
     return scores, rows
 
 
+def _fuse_list_mode(mode, who: str) -> int:
+    m = fusion_mode(mode) if isinstance(mode, str) else int(mode)
+    if m is None or m == N.SR_FUSE_FLOOR_FULL:
+        raise ValueError(f"{who}: mode must be 'relative' or 'floor' ('floor_full' is 'floor' with "
+                         "side_a and side_b)")
+    return m
+
+
 def score_fuse(score_a, rows_a, score_b, rows_b, k: int, mode: str = "relative", alpha: float = 0.5,
                side_a=None, floor_a: float = -1.0, floor_b: float = 0.0,
-               min_score: float = float("-inf"), device: int = 0):
+               min_score: float = float("-inf"), device: int = 0, side_b=None):
     """Device score fusion of two scored row lists per query (sr_score_fuse; host arrays score
     [B, ka] fp32 / rows [B, ka] int64 and the same with kb; row < 0 = absent; ``side_a`` [B, kb]:
-    the a-metric score of each b row, -inf = unknown).  ``mode``: "relative" (min-max of each
+    the a-metric score of each b row, -inf = unknown; ``side_b`` [B, ka]: its mirror, the b-metric
+    score of each a row, sr_score_fuse_sides).  ``mode``: "relative" (min-max of each
     list) or "floor" (lo = floor_a / floor_b).  Returns (fused [B,k] fp32 desc, rows [B,k] int64,
     a [B,k] fp32, b [B,k] fp32): -inf / -1 / -inf / -inf in unfilled slots."""
-    m = fusion_mode(mode) if isinstance(mode, str) else int(mode)
-    if m is None:
-        raise ValueError("score_fuse: mode must be 'relative' or 'floor'")
+    m = _fuse_list_mode(mode, "score_fuse")
     N.require_gpu()
     ra = np.ascontiguousarray(np.asarray(rows_a, dtype=np.int64))
     rb = np.ascontiguousarray(np.asarray(rows_b, dtype=np.int64))
@@ -560,23 +662,27 @@ def score_fuse(score_a, rows_a, score_b, rows_b, k: int, mode: str = "relative",
     ka, kb = ra.shape[1], rb.shape[1]
     k = int(k)
     out = [np.empty((Bq, max(k, 0)), dtype=t) for t in (np.float32, np.int64, np.float32, np.float32)]
-    N.call("sr_score_fuse", N.ptr(sa) if ka and Bq else None, N.ptr(ra) if ka and Bq else None, ka,
-           N.ptr(sb) if kb and Bq else None, N.ptr(rb) if kb and Bq else None, kb,
-           N.ptr(sd) if (sd is not None and kb and Bq) else None, Bq, m, float(alpha), float(floor_a),
-           float(floor_b), float(min_score), k, N.ptr(out[0]), N.ptr(out[1]), N.ptr(out[2]),
-           N.ptr(out[3]), int(device))
+    lists = (N.ptr(sa) if ka and Bq else None, N.ptr(ra) if ka and Bq else None, ka,
+             N.ptr(sb) if kb and Bq else None, N.ptr(rb) if kb and Bq else None, kb,
+             N.ptr(sd) if (sd is not None and kb and Bq) else None)
+    tail = (Bq, m, float(alpha), float(floor_a), float(floor_b), float(min_score), k, N.ptr(out[0]),
+            N.ptr(out[1]), N.ptr(out[2]), N.ptr(out[3]), int(device))
+    if side_b is None:
+        N.call("sr_score_fuse", *lists, *tail)
+    else:
+        sdb = np.ascontiguousarray(np.asarray(side_b, dtype=np.float32).reshape(ra.shape))
+        N.call("sr_score_fuse_sides", *lists, N.ptr(sdb) if ka and Bq else None, *tail)
     return tuple(out)
 
 
 def score_fuse_dev(score_a, rows_a, score_b, rows_b, k: int, mode: str = "relative",
                    alpha: float = 0.5, side_a=None, floor_a: float = -1.0, floor_b: float = 0.0,
-                   min_score: float = float("-inf"), stream=None):
-    """score_fuse on device tensors (torch fp32 / int64 [B, ka], [B, kb]; sr_score_fuse_dev),
-    asynchronous on ``stream`` -> device tensors (fused, rows, a, b) [B, k]."""
+                   min_score: float = float("-inf"), stream=None, side_b=None):
+    """score_fuse on device tensors (torch fp32 / int64 [B, ka], [B, kb]; sr_score_fuse_dev, or
+    sr_score_fuse_sides_dev with ``side_b`` [B, ka]), asynchronous on ``stream`` -> device tensors
+    (fused, rows, a, b) [B, k]."""
     import torch
-    m = fusion_mode(mode) if isinstance(mode, str) else int(mode)
-    if m is None:
-        raise ValueError("score_fuse_dev: mode must be 'relative' or 'floor'")
+    m = _fuse_list_mode(mode, "score_fuse_dev")
     ra, rb = rows_a.contiguous(), rows_b.contiguous()
     sa, sb = score_a.contiguous(), score_b.contiguous()
     assert ra.is_cuda and ra.dtype == torch.int64 and rb.dtype == torch.int64
@@ -590,10 +696,16 @@ def score_fuse_dev(score_a, rows_a, score_b, rows_b, k: int, mode: str = "relati
     dev = ra.device
     out = [torch.empty((Bq, max(k, 0)), dtype=t, device=dev)
            for t in (torch.float32, torch.int64, torch.float32, torch.float32)]
-    N.call("sr_score_fuse_dev", N.ptr(sa), N.ptr(ra), ra.shape[1], N.ptr(sb), N.ptr(rb), rb.shape[1],
-           None if sd is None else N.ptr(sd), Bq, m, float(alpha), float(floor_a), float(floor_b),
-           float(min_score), k, N.ptr(out[0]), N.ptr(out[1]), N.ptr(out[2]), N.ptr(out[3]),
-           dev.index or 0, N.stream_handle(stream))
+    lists = (N.ptr(sa), N.ptr(ra), ra.shape[1], N.ptr(sb), N.ptr(rb), rb.shape[1],
+             None if sd is None else N.ptr(sd))
+    tail = (Bq, m, float(alpha), float(floor_a), float(floor_b), float(min_score), k, N.ptr(out[0]),
+            N.ptr(out[1]), N.ptr(out[2]), N.ptr(out[3]), dev.index or 0, N.stream_handle(stream))
+    if side_b is None:
+        N.call("sr_score_fuse_dev", *lists, *tail)
+    else:
+        sdb = side_b.contiguous()
+        assert sdb.dtype == torch.float32 and sdb.shape == ra.shape
+        N.call("sr_score_fuse_sides_dev", *lists, N.ptr(sdb), *tail)
     return tuple(out)
 
 
@@ -603,8 +715,9 @@ def hybrid_search(store, lex: NativeLexIndex, queries, query_terms: Sequence[Seq
                   fusion: str = "rrf", alpha: float = 0.5, components: bool = False):
     """Dense top-k_each (cosine, store) and BM25 top-k_each (lex) fused on the device.
     ``fusion`` "rrf" (default): reciprocal rank -> (rrf score [B,k] fp64 desc, rows [B,k] int64).
-    "relative" / "floor": score fusion (sr_hybrid_search_fused) with ``alpha`` the weight of the
-    dense side -> (fused score [B,k] fp32 desc, rows [B,k] int64), and with ``components`` also the
+    "relative" / "floor" / "floor_full": score fusion (sr_hybrid_search_fused) with ``alpha`` the
+    weight of the dense side ("floor" completes the dense side with the exact cosines of the BM25
+    rows, "floor_full" also the BM25 side with the exact BM25 of the dense rows) -> (fused score [B,k] fp32 desc, rows [B,k] int64), and with ``components`` also the
     cosine and the BM25 score of each kept row (-inf where unknown)."""
     mode = fusion_mode(fusion)
     q = np.ascontiguousarray(np.asarray(queries, dtype=np.float32))
@@ -639,8 +752,8 @@ def hybrid_search(store, lex: NativeLexIndex, queries, query_terms: Sequence[Seq
 _rrf_impl = [lambda a, b, k, rc, ms, dev: rrf_fuse(a, b, k, rc, ms, dev)]
 
 
-def _fuse_native(sa, ra, sb, rb, side, mode, alpha, fa, fb, ms, k, dev):
-    return score_fuse(sa, ra, sb, rb, k, mode, alpha, side, fa, fb, ms, dev)
+def _fuse_native(sa, ra, sb, rb, side, mode, alpha, fa, fb, ms, k, dev, side_b=None):
+    return score_fuse(sa, ra, sb, rb, k, mode, alpha, side, fa, fb, ms, dev, side_b=side_b)
 
 
 _fuse_impl = [_fuse_native]
@@ -654,5 +767,5 @@ def set_rrf_backend(fn) -> None:
 def set_fuse_backend(fn) -> None:
     """Test seam: replace the host-list score fusion used by ShardedLex.hybrid (CPU doubles);
     fn(score_a, rows_a, score_b, rows_b, side_a, mode, alpha, floor_a, floor_b, min_score, k,
-    device) -> (fused, rows, a, b)."""
+    device[, side_b=...]) -> (fused, rows, a, b); side_b is passed only for "floor_full"."""
     _fuse_impl[0] = fn or _fuse_native

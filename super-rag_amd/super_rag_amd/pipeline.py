@@ -130,6 +130,11 @@ class SearchPipeline:
         # BM25 rows, which this rank can read only while every candidate row is its own
         from .lexical import check_alpha, fusion_mode
         self.fusion = str(fusion)
+        if self.fusion == "floor_full":
+            # its BM25 completion scores host-side query terms (sr_lex_score_rows_dev); the pipeline's
+            # queries are device tokens
+            raise ValueError("fusion 'floor_full' is not built for the device pipeline (no "
+                             "device-token variant of lex_score_rows); use 'floor' or 'relative'")
         self.fuse_mode = fusion_mode(self.fusion)
         self.alpha = check_alpha(alpha)
         if self.fusion == "floor" and self.exchange:

@@ -13,7 +13,7 @@ Opt-in lexical retrieval (ctx ``fulltext``): every added node's text is also ind
 the device (lexical.py, k_lex.hip); ``fulltext_search(text, top_k, keywords)`` backs the
 reference's ``fulltext_search`` node type, and ctx ``hybrid`` makes ``search`` fuse the dense and
 the BM25 rankings by reciprocal rank on the device (score = rrf score, descending) or, with ctx
-``hybrid_fusion`` "relative" / "floor" and ``hybrid_alpha`` (the weight of the dense side), by their
+``hybrid_fusion`` "relative" / "floor" / "floor_full" and ``hybrid_alpha`` (the weight of the dense side), by their
 normalised scores (k_fuse.hip; score = fused score, descending).  Both work on
 collections sharded over several devices (ctx ``devices``: lexical.ShardedLex, corpus-wide BM25
 statistics), with the same results as one device.
@@ -406,8 +406,9 @@ class MI355XVectorStoreConnector:
         self.fulltext = bool(ctx.get("fulltext", False)) or self.hybrid
         self.hybrid_k_each = ctx.get("hybrid_k_each")
         self.rrf_rank_const = int(ctx.get("rrf_rank_const", 1))
-        # opt-in score fusion (k_fuse.hip): "relative" (min-max of each list) or "floor" (cosine from
-        # -1, BM25 from 0, dense side completed); hybrid_alpha = the weight of the dense side
+        # opt-in score fusion (k_fuse.hip): "relative" (min-max of each list), "floor" (cosine from
+        # -1, BM25 from 0, dense side completed) or "floor_full" (floor with the BM25 side completed
+        # too, lex_score_rows); hybrid_alpha = the weight of the dense side
         from .lexical import check_alpha, fusion_mode
         self.hybrid_fusion = str(ctx.get("hybrid_fusion", "rrf"))
         fusion_mode(self.hybrid_fusion)          # ValueError for an unknown name
