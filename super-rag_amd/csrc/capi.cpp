@@ -272,40 +272,29 @@ int sr_mmr_rerank(const float* q, const float* cand, const int32_t* n_cand, int 
   sr::DeviceGuard g(device);
   const int64_t ld = sr::round_up(dim, 64);
   const int64_t nc = (int64_t)B * K, no = (int64_t)B * k_out;
-  // workspace: fp32 inputs | fp16 rows | n_cand | outputs (every part a multiple of 16 bytes)
-  const size_t b_q32 = (size_t)sr::round_up((int64_t)B * dim * 4, 16);
-  const size_t b_c32 = (size_t)sr::round_up(nc * dim * 4, 16);
-  const size_t b_q16 = (size_t)B * ld * 2, b_c16 = (size_t)nc * ld * 2;
-  const size_t b_n = (size_t)sr::round_up((int64_t)B * 4, 16), b_o = (size_t)sr::round_up(no * 4, 16);
+  float *q32, *c32, *ds;
+  sr::half_t *q16, *c16;  // the normalised rows the kernel reads
+  int32_t *dn, *di;
+  sr::Carve c;
+  c.part((size_t)B * dim, &q32);
+  c.part((size_t)nc * dim, &c32);
+  c.part((size_t)B * ld, &q16);
+  c.part((size_t)nc * ld, &c16);
+  c.part((size_t)B, &dn);
+  c.part((size_t)no, &ds, &di);
   sr::DevBuf ws;
-  ws.reserve(b_q32 + b_c32 + b_q16 + b_c16 + b_n + 2 * b_o);
-  char* w = ws.as<char>();
-  float* q32 = reinterpret_cast<float*>(w);
-  float* c32 = reinterpret_cast<float*>(w + b_q32);
-  sr::half_t* q16 = reinterpret_cast<sr::half_t*>(w + b_q32 + b_c32);
-  sr::half_t* c16 = reinterpret_cast<sr::half_t*>(w + b_q32 + b_c32 + b_q16);
-  int32_t* dn = reinterpret_cast<int32_t*>(w + b_q32 + b_c32 + b_q16 + b_c16);
-  float* ds = reinterpret_cast<float*>(w + b_q32 + b_c32 + b_q16 + b_c16 + b_n);
-  int32_t* di = reinterpret_cast<int32_t*>(w + b_q32 + b_c32 + b_q16 + b_c16 + b_n + b_o);
-  hipStream_t st = nullptr;
-  SR_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  try {
-    SR_HIP(hipMemcpyAsync(q32, q, (size_t)B * dim * 4, hipMemcpyHostToDevice, st));
-    SR_HIP(hipMemcpyAsync(c32, cand, (size_t)nc * dim * 4, hipMemcpyHostToDevice, st));
-    if (n_cand) SR_HIP(hipMemcpyAsync(dn, n_cand, (size_t)B * 4, hipMemcpyHostToDevice, st));
-    sr::launch_normalize_rows(q32, SR_DTYPE_F32, B, dim, q16, (int)ld, st);
-    sr::launch_normalize_rows(c32, SR_DTYPE_F32, nc, dim, c16, (int)ld, st);
-    sr::launch_mmr_rerank(c16, ld, nc, nullptr, 0, n_cand ? dn : nullptr, nullptr, q16, B, K, lambda,
-                          mode, min_score, k_out, ds, nullptr, di, nullptr, st);
-    SR_HIP(hipMemcpyAsync(out_score, ds, (size_t)no * 4, hipMemcpyDeviceToHost, st));
-    SR_HIP(hipMemcpyAsync(out_index, di, (size_t)no * 4, hipMemcpyDeviceToHost, st));
-    SR_HIP(hipStreamSynchronize(st));
-  } catch (...) {
-    (void)hipStreamSynchronize(st);
-    (void)hipStreamDestroy(st);
-    throw;
-  }
-  SR_HIP(hipStreamDestroy(st));
+  ws.carve(c);
+  sr::ScopedStream st;
+  SR_HIP(hipMemcpyAsync(q32, q, (size_t)B * dim * 4, hipMemcpyHostToDevice, st));
+  SR_HIP(hipMemcpyAsync(c32, cand, (size_t)nc * dim * 4, hipMemcpyHostToDevice, st));
+  if (n_cand) SR_HIP(hipMemcpyAsync(dn, n_cand, (size_t)B * 4, hipMemcpyHostToDevice, st));
+  sr::launch_normalize_rows(q32, SR_DTYPE_F32, B, dim, q16, (int)ld, st);
+  sr::launch_normalize_rows(c32, SR_DTYPE_F32, nc, dim, c16, (int)ld, st);
+  sr::launch_mmr_rerank(c16, ld, nc, nullptr, 0, n_cand ? dn : nullptr, nullptr, q16, B, K, lambda,
+                        mode, min_score, k_out, ds, nullptr, di, nullptr, st);
+  SR_HIP(hipMemcpyAsync(out_score, ds, (size_t)no * 4, hipMemcpyDeviceToHost, st));
+  SR_HIP(hipMemcpyAsync(out_index, di, (size_t)no * 4, hipMemcpyDeviceToHost, st));
+  SR_HIP(hipStreamSynchronize(st));
   SR_API_END
 }
 
@@ -744,29 +733,22 @@ int sr_rrf_fuse(const int64_t* rows_a, int ka, const int64_t* rows_b, int kb, in
   if (ka > 0) SR_NONNULL(rows_a);
   if (kb > 0) SR_NONNULL(rows_b);
   sr::DeviceGuard g(device);
-  const size_t ba = (size_t)B * ka * 8, bb = (size_t)B * kb * 8, bo = (size_t)B * k_out * 8;
+  const size_t na = (size_t)B * ka, nb = (size_t)B * kb, no = (size_t)B * k_out;
+  int64_t *da, *db, *dr;
+  double* ds;
+  sr::Carve c;
+  c.part(na, &da);
+  c.part(nb, &db);
+  c.part(no, &ds, &dr);
   sr::DevBuf ws;
-  ws.reserve(ba + bb + 2 * bo + 8);
-  char* w = ws.as<char>();
-  int64_t* da = reinterpret_cast<int64_t*>(w);
-  int64_t* db = reinterpret_cast<int64_t*>(w + ba);
-  double* ds = reinterpret_cast<double*>(w + ba + bb);
-  int64_t* dr = reinterpret_cast<int64_t*>(w + ba + bb + bo);
-  hipStream_t st = nullptr;
-  SR_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  try {
-    if (ba) SR_HIP(hipMemcpyAsync(da, rows_a, ba, hipMemcpyHostToDevice, st));
-    if (bb) SR_HIP(hipMemcpyAsync(db, rows_b, bb, hipMemcpyHostToDevice, st));
-    sr::launch_rrf_fuse(da, ka, db, kb, B, rank_const, min_score, k_out, ds, dr, st);
-    SR_HIP(hipMemcpyAsync(out_score, ds, bo, hipMemcpyDeviceToHost, st));
-    SR_HIP(hipMemcpyAsync(out_rows, dr, bo, hipMemcpyDeviceToHost, st));
-    SR_HIP(hipStreamSynchronize(st));
-  } catch (...) {
-    (void)hipStreamSynchronize(st);
-    (void)hipStreamDestroy(st);
-    throw;
-  }
-  SR_HIP(hipStreamDestroy(st));
+  ws.carve(c);
+  sr::ScopedStream st;
+  if (na) SR_HIP(hipMemcpyAsync(da, rows_a, na * 8, hipMemcpyHostToDevice, st));
+  if (nb) SR_HIP(hipMemcpyAsync(db, rows_b, nb * 8, hipMemcpyHostToDevice, st));
+  sr::launch_rrf_fuse(da, ka, db, kb, B, rank_const, min_score, k_out, ds, dr, st);
+  SR_HIP(hipMemcpyAsync(out_score, ds, no * 8, hipMemcpyDeviceToHost, st));
+  SR_HIP(hipMemcpyAsync(out_rows, dr, no * 8, hipMemcpyDeviceToHost, st));
+  SR_HIP(hipStreamSynchronize(st));
   SR_API_END
 }
 
@@ -808,25 +790,24 @@ int sr_hybrid_search(sr_store* s, sr_lex* x, const float* q, const int64_t* qoff
   SR_CHECK(lrows == st.rows(), "hybrid: store and lexical index hold different row counts");
   sr::DeviceGuard g(st.device());
   hipStream_t sm = lx.stream();
-  const size_t bq = (size_t)B * st.dim() * 4, be = (size_t)B * k_each * 8, bo = (size_t)B * k * 8;
+  const size_t nq = (size_t)B * st.dim(), ne = (size_t)B * k_each, no = (size_t)B * k;
+  float *dq, *dsim, *lsc;
+  int64_t *drow, *lrow, *orow;
+  double* os;
+  sr::Carve c;
+  c.part(nq, &dq);
+  c.part(ne, &dsim, &drow, &lsc, &lrow);
+  c.part(no, &os, &orow);
   sr::DevBuf ws;
-  ws.reserve(bq + 4 * be + 2 * bo + 64);
-  char* w = ws.as<char>();
-  float* dq = reinterpret_cast<float*>(w);
-  float* dsim = reinterpret_cast<float*>(w + bq);
-  int64_t* drow = reinterpret_cast<int64_t*>(w + bq + be);
-  float* lsc = reinterpret_cast<float*>(w + bq + 2 * be);
-  int64_t* lrow = reinterpret_cast<int64_t*>(w + bq + 3 * be);
-  double* os = reinterpret_cast<double*>(w + bq + 4 * be);
-  int64_t* orow = reinterpret_cast<int64_t*>(w + bq + 4 * be + bo);
+  ws.carve(c);
   const uint8_t* elig = st.eligibility(allow, mask_key);
   lx.begin(sm);
-  SR_HIP(hipMemcpyAsync(dq, q, bq, hipMemcpyHostToDevice, sm));
+  SR_HIP(hipMemcpyAsync(dq, q, nq * 4, hipMemcpyHostToDevice, sm));
   st.search_dev(dq, SR_DTYPE_F32, B, k_each, dsim, drow, 0, sm, elig);
   lx.search_dev(qoff, qterms, B, k_each, allow, mask_key, lsc, lrow, sm);
   sr::launch_rrf_fuse(drow, k_each, lrow, k_each, B, rank_const, min_score, k, os, orow, sm);
-  SR_HIP(hipMemcpyAsync(out_score, os, bo, hipMemcpyDeviceToHost, sm));
-  SR_HIP(hipMemcpyAsync(out_rows, orow, bo, hipMemcpyDeviceToHost, sm));
+  SR_HIP(hipMemcpyAsync(out_score, os, no * 8, hipMemcpyDeviceToHost, sm));
+  SR_HIP(hipMemcpyAsync(out_rows, orow, no * 8, hipMemcpyDeviceToHost, sm));
   lx.end(sm);
   SR_HIP(hipStreamSynchronize(sm));
   SR_API_END
@@ -855,48 +836,34 @@ int sr_score_fuse_sides(const float* score_a, const int64_t* rows_a, int ka, con
   for (int64_t i = 0; i < (int64_t)B * kb; ++i)
     SR_CHECK(rows_b[i] <= 0xfffffffeLL, "score_fuse: rows must be in [0, 2^32 - 2] (or < 0: absent)");
   sr::DeviceGuard g(device);
-  // staging: rows a | rows b | out rows | score a | score b | side a | out score | out a | out b |
-  // side b
   const size_t na = (size_t)B * ka, nb = (size_t)B * kb, no = (size_t)B * k_out;
+  int64_t *da_r, *db_r, *do_r;
+  float *da_s, *db_s, *dside, *dsideb, *do_s, *do_a, *do_b;
+  sr::Carve c;
+  c.part(na, &da_r, &da_s, &dsideb);  // side b scores the rows of list a
+  c.part(nb, &db_r, &db_s, &dside);   // and side a those of list b
+  c.part(no, &do_r, &do_s, &do_a, &do_b);
   sr::DevBuf ws;
-  ws.reserve((na + nb + no) * 8 + (2 * na + 2 * nb + 3 * no) * 4 + 8);
-  int64_t* da_r = ws.as<int64_t>();
-  int64_t* db_r = da_r + na;
-  int64_t* do_r = db_r + nb;
-  float* da_s = reinterpret_cast<float*>(do_r + no);
-  float* db_s = da_s + na;
-  float* dside = db_s + nb;
-  float* do_s = dside + nb;
-  float* do_a = do_s + no;
-  float* do_b = do_a + no;
-  float* dsideb = do_b + no;
-  hipStream_t st = nullptr;
-  SR_HIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  try {
-    if (na) {
-      SR_HIP(hipMemcpyAsync(da_r, rows_a, na * 8, hipMemcpyHostToDevice, st));
-      SR_HIP(hipMemcpyAsync(da_s, score_a, na * 4, hipMemcpyHostToDevice, st));
-      if (side_b) SR_HIP(hipMemcpyAsync(dsideb, side_b, na * 4, hipMemcpyHostToDevice, st));
-    }
-    if (nb) {
-      SR_HIP(hipMemcpyAsync(db_r, rows_b, nb * 8, hipMemcpyHostToDevice, st));
-      SR_HIP(hipMemcpyAsync(db_s, score_b, nb * 4, hipMemcpyHostToDevice, st));
-      if (side_a) SR_HIP(hipMemcpyAsync(dside, side_a, nb * 4, hipMemcpyHostToDevice, st));
-    }
-    sr::launch_score_fuse(da_s, da_r, ka, db_s, db_r, kb, side_a ? dside : nullptr, B, mode, alpha,
-                          floor_a, floor_b, min_score, k_out, do_s, do_r, out_a ? do_a : nullptr,
-                          out_b ? do_b : nullptr, st, side_b ? dsideb : nullptr);
-    SR_HIP(hipMemcpyAsync(out_score, do_s, no * 4, hipMemcpyDeviceToHost, st));
-    SR_HIP(hipMemcpyAsync(out_rows, do_r, no * 8, hipMemcpyDeviceToHost, st));
-    if (out_a) SR_HIP(hipMemcpyAsync(out_a, do_a, no * 4, hipMemcpyDeviceToHost, st));
-    if (out_b) SR_HIP(hipMemcpyAsync(out_b, do_b, no * 4, hipMemcpyDeviceToHost, st));
-    SR_HIP(hipStreamSynchronize(st));
-  } catch (...) {
-    (void)hipStreamSynchronize(st);
-    (void)hipStreamDestroy(st);
-    throw;
+  ws.carve(c);
+  sr::ScopedStream st;
+  if (na) {
+    SR_HIP(hipMemcpyAsync(da_r, rows_a, na * 8, hipMemcpyHostToDevice, st));
+    SR_HIP(hipMemcpyAsync(da_s, score_a, na * 4, hipMemcpyHostToDevice, st));
+    if (side_b) SR_HIP(hipMemcpyAsync(dsideb, side_b, na * 4, hipMemcpyHostToDevice, st));
   }
-  SR_HIP(hipStreamDestroy(st));
+  if (nb) {
+    SR_HIP(hipMemcpyAsync(db_r, rows_b, nb * 8, hipMemcpyHostToDevice, st));
+    SR_HIP(hipMemcpyAsync(db_s, score_b, nb * 4, hipMemcpyHostToDevice, st));
+    if (side_a) SR_HIP(hipMemcpyAsync(dside, side_a, nb * 4, hipMemcpyHostToDevice, st));
+  }
+  sr::launch_score_fuse(da_s, da_r, ka, db_s, db_r, kb, side_a ? dside : nullptr, B, mode, alpha,
+                        floor_a, floor_b, min_score, k_out, do_s, do_r, out_a ? do_a : nullptr,
+                        out_b ? do_b : nullptr, st, side_b ? dsideb : nullptr);
+  SR_HIP(hipMemcpyAsync(out_score, do_s, no * 4, hipMemcpyDeviceToHost, st));
+  SR_HIP(hipMemcpyAsync(out_rows, do_r, no * 8, hipMemcpyDeviceToHost, st));
+  if (out_a) SR_HIP(hipMemcpyAsync(out_a, do_a, no * 4, hipMemcpyDeviceToHost, st));
+  if (out_b) SR_HIP(hipMemcpyAsync(out_b, do_b, no * 4, hipMemcpyDeviceToHost, st));
+  SR_HIP(hipStreamSynchronize(st));
   SR_API_END
 }
 
@@ -992,24 +959,16 @@ int sr_hybrid_search_fused(sr_store* s, sr_lex* x, const float* q, const int64_t
   SR_CHECK(lrows == st.rows(), "hybrid: store and lexical index hold different row counts");
   sr::DeviceGuard g(st.device());
   hipStream_t sm = lx.stream();
-  // staging: queries | dense rows | lex rows | out rows | dense sims | lex scores | side | out x 3 |
-  // side b
-  const size_t bq = (size_t)sr::round_up((int64_t)B * st.dim() * 4, 16);
   const size_t ne = (size_t)B * k_each, no = (size_t)B * k;
+  float *dq, *dsim, *lsc, *side, *sideb, *os, *oa, *ob;
+  int64_t *drow, *lrow, *orow;
+  sr::Carve c;
+  c.part((size_t)B * st.dim(), &dq);
+  c.part(ne, &drow, &dsim, &sideb);  // the dense list, and its rows' exact BM25 ("floor_full")
+  c.part(ne, &lrow, &lsc, &side);    // the BM25 list, and its rows' exact cosines (floor modes)
+  c.part(no, &orow, &os, &oa, &ob);
   sr::DevBuf ws;
-  ws.reserve(bq + (2 * ne + no) * 8 + (4 * ne + 3 * no) * 4 + 64);
-  char* w = ws.as<char>();
-  float* dq = reinterpret_cast<float*>(w);
-  int64_t* drow = reinterpret_cast<int64_t*>(w + bq);
-  int64_t* lrow = drow + ne;
-  int64_t* orow = lrow + ne;
-  float* dsim = reinterpret_cast<float*>(orow + no);
-  float* lsc = dsim + ne;
-  float* side = lsc + ne;
-  float* os = side + ne;
-  float* oa = os + no;
-  float* ob = oa + no;
-  float* sideb = ob + no;
+  ws.carve(c);
   const bool full = mode == SR_FUSE_FLOOR_FULL;
   const bool floor_mode = mode == SR_FUSE_FLOOR || full;
   const uint8_t* elig = st.eligibility(allow, mask_key);

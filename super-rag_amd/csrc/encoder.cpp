@@ -567,12 +567,13 @@ void Encoder::forward_host(const int32_t* ids, const int32_t* mask, const int32_
   DeviceGuard g(device_);
   const int64_t n = (int64_t)B * S;
   const int64_t out_elems = (int64_t)B * (mode == 0 ? cfg_.hidden : cfg_.num_labels);
-  const size_t in_bytes = (size_t)n * sizeof(int32_t) * (types ? 3 : 2);
-  hostio_.reserve(in_bytes + (size_t)out_elems * sizeof(float));
-  int32_t* dids = hostio_.as<int32_t>();
-  int32_t* dmask = dids + n;
-  int32_t* dtypes = types ? dmask + n : nullptr;
-  float* dout = reinterpret_cast<float*>(hostio_.as<char>() + in_bytes);
+  int32_t *dids, *dmask, *dtypes = nullptr;
+  float* dout;
+  Carve c;
+  c.part((size_t)n, &dids, &dmask);
+  if (types) c.part((size_t)n, &dtypes);
+  c.part((size_t)out_elems, &dout);
+  hostio_.carve(c);
   SR_HIP(hipMemcpyAsync(dids, ids, n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
   SR_HIP(hipMemcpyAsync(dmask, mask, n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
   if (types) SR_HIP(hipMemcpyAsync(dtypes, types, n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));

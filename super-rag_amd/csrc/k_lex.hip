@@ -845,6 +845,28 @@ struct LexStatsHost {
   }
 };
 
+// The workspace of one group of queries in search_dev / search_tok_dev: the term slots, each query's
+// first slot, first key and key count, each slot's row-block bounds, the candidate keys, avgdl.
+struct LexWs {
+  LexTerm* slots;
+  int* slot_off;
+  int64_t* key_off;
+  int* key_cnt;
+  int32_t* bounds;
+  uint64_t* keys;
+  float* avgdl;
+  LexWs(DevBuf& buf, size_t queries, size_t n_slots, size_t n_bounds, size_t n_keys) {
+    Carve c;
+    c.part(n_slots, &slots);
+    c.part(queries + 1, &slot_off, &key_off);
+    c.part(queries, &key_cnt);
+    c.part(n_bounds, &bounds);
+    c.part(n_keys, &keys);
+    c.part(1, &avgdl);
+    buf.carve(c);
+  }
+};
+
 }  // namespace
 
 void LexIndex::search_dev(const int64_t* qoff, const int32_t* qterms, int B, int k,
@@ -906,27 +928,9 @@ void LexIndex::search_dev(const int64_t* qoff, const int32_t* qterms, int B, int
       slot_off[(size_t)i + 1] = (int)slots.size();
     }
     const int nslots = (int)slots.size();
-    const size_t b_sl = std::max<size_t>(slots.size(), 1) * sizeof(LexTerm);
     const size_t b_so = (size_t)(qb + 1) * 4, b_ko = (size_t)(qb + 1) * 8, b_cnt = (size_t)qb * 4;
-    const size_t b_bnd = (size_t)std::max(nslots, 1) * (NB + 1) * 4;
-    const size_t b_keys = (size_t)std::max<int64_t>(koff[(size_t)qb], 1) * 8;
-    size_t o = 0;
-    auto carve = [&](size_t bytes) {
-      const size_t at = o;
-      o += (size_t)round_up((int64_t)bytes, 256);
-      return at;
-    };
-    const size_t o_sl = carve(b_sl), o_so = carve(b_so), o_ko = carve(b_ko), o_cnt = carve(b_cnt),
-                 o_bnd = carve(b_bnd), o_keys = carve(b_keys), o_avg = carve(4);
-    ws_.reserve(o);
-    char* w = ws_.as<char>();
-    LexTerm* d_sl = reinterpret_cast<LexTerm*>(w + o_sl);
-    int* d_so = reinterpret_cast<int*>(w + o_so);
-    int64_t* d_ko = reinterpret_cast<int64_t*>(w + o_ko);
-    int* d_cnt = reinterpret_cast<int*>(w + o_cnt);
-    int32_t* d_bnd = reinterpret_cast<int32_t*>(w + o_bnd);
-    uint64_t* d_keys = reinterpret_cast<uint64_t*>(w + o_keys);
-    float* d_avg = reinterpret_cast<float*>(w + o_avg);
+    const auto [d_sl, d_so, d_ko, d_cnt, d_bnd, d_keys, d_avg] =
+        LexWs(ws_, (size_t)qb, (size_t)nslots, (size_t)nslots * (NB + 1), (size_t)koff[(size_t)qb]);
     uint32_t adl_bits;
     std::memcpy(&adl_bits, &adl, 4);
     SR_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_avg), (int)adl_bits, 1, s));
@@ -1030,25 +1034,8 @@ void LexIndex::search_tok_dev(const int32_t* tok, const int32_t* qlen, int B, in
     }
   }
   const int64_t nslots = (int64_t)G_alloc * Lq;
-  size_t o = 0;
-  auto carve = [&](size_t bytes) {
-    const size_t at = o;
-    o += (size_t)round_up((int64_t)std::max<size_t>(bytes, 1), 256);
-    return at;
-  };
-  const size_t o_sl = carve((size_t)nslots * sizeof(LexTerm)), o_so = carve((size_t)(G_alloc + 1) * 4),
-               o_ko = carve((size_t)(G_alloc + 1) * 8), o_cnt = carve((size_t)G_alloc * 4),
-               o_bnd = carve((size_t)nslots * (NB + 1) * 4), o_keys = carve((size_t)keys_alloc * 8),
-               o_avg = carve(4);
-  ws_.reserve(o);
-  char* w = ws_.as<char>();
-  LexTerm* d_sl = reinterpret_cast<LexTerm*>(w + o_sl);
-  int* d_so = reinterpret_cast<int*>(w + o_so);
-  int64_t* d_ko = reinterpret_cast<int64_t*>(w + o_ko);
-  int* d_cnt = reinterpret_cast<int*>(w + o_cnt);
-  int32_t* d_bnd = reinterpret_cast<int32_t*>(w + o_bnd);
-  uint64_t* d_keys = reinterpret_cast<uint64_t*>(w + o_keys);
-  float* d_avg = reinterpret_cast<float*>(w + o_avg);
+  const auto [d_sl, d_so, d_ko, d_cnt, d_bnd, d_keys, d_avg] =
+      LexWs(ws_, (size_t)G_alloc, (size_t)nslots, (size_t)nslots * (NB + 1), (size_t)keys_alloc);
   for (const auto& [b0, qb] : groups) {
     hipLaunchKernelGGL(lex_qprep_kernel, dim3(1), dim3(1024), 0, s, tok + (int64_t)b0 * Lq, qlen + b0,
                        qb, Lq, off_.as<int64_t>(), vocab_, rows_, live_n_, sum_dl_, gstats,
@@ -1085,11 +1072,13 @@ void LexIndex::search_host(const int64_t* qoff, const int32_t* qterms, int B, in
   SR_CHECK(out_score && out_rows, "lex.search: null output");
   DeviceGuard g(device_);
   const size_t ob = (size_t)B * k;
-  const size_t o_rows = (size_t)round_up((int64_t)ob * 4, 16), o_fix = o_rows + ob * 8;
-  out_.reserve(o_fix + (out_fixed ? ob * 4 : 0));
-  float* ds = out_.as<float>();
-  int64_t* dr = reinterpret_cast<int64_t*>(out_.as<char>() + o_rows);
-  uint32_t* dfx = out_fixed ? reinterpret_cast<uint32_t*>(out_.as<char>() + o_fix) : nullptr;
+  float* ds;
+  int64_t* dr;
+  uint32_t* dfx = nullptr;
+  Carve c;
+  c.part(ob, &ds, &dr);
+  if (out_fixed) c.part(ob, &dfx);
+  out_.carve(c);
   search_dev(qoff, qterms, B, k, allow, mask_key, ds, dr, stream_, glob, 0, dfx);
   SR_HIP(hipMemcpyAsync(out_score, ds, ob * 4, hipMemcpyDeviceToHost, stream_));
   SR_HIP(hipMemcpyAsync(out_rows, dr, ob * 8, hipMemcpyDeviceToHost, stream_));
@@ -1127,19 +1116,13 @@ void LexIndex::score_rows_dev(const int64_t* qoff, const int32_t* qterms, int B,
     qt_off[(size_t)b + 1] = (int)term.size();
   }
   const size_t nt = term.size();
-  size_t o = 0;
-  auto carve = [&](size_t bytes) {
-    const size_t at = o;
-    o += (size_t)round_up((int64_t)std::max<size_t>(bytes, 1), 256);
-    return at;
-  };
-  const size_t o_off = carve(qt_off.size() * 4), o_t = carve(nt * 4), o_i = carve(nt * 4), o_m = carve(nt * 4);
-  ws_.reserve(o);
-  char* w = ws_.as<char>();
-  int* d_off = reinterpret_cast<int*>(w + o_off);
-  int32_t* d_t = reinterpret_cast<int32_t*>(w + o_t);
-  float* d_i = reinterpret_cast<float*>(w + o_i);
-  int32_t* d_m = reinterpret_cast<int32_t*>(w + o_m);
+  int* d_off;
+  int32_t *d_t, *d_m;
+  float* d_i;
+  Carve c;
+  c.part(qt_off.size(), &d_off);
+  c.part(nt, &d_t, &d_i, &d_m);
+  ws_.carve(c);
   SR_HIP(hipMemcpyAsync(d_off, qt_off.data(), qt_off.size() * 4, hipMemcpyHostToDevice, s));
   if (nt) {
     SR_HIP(hipMemcpyAsync(d_t, term.data(), nt * 4, hipMemcpyHostToDevice, s));
@@ -1170,10 +1153,12 @@ void LexIndex::score_rows_host(const int64_t* qoff, const int32_t* qterms, int B
   SR_CHECK(rows && out_score, "lex.score_rows: null buffer");
   DeviceGuard g(device_);
   const size_t n = (size_t)B * K;
-  out_.reserve(n * 16);   // rows | score | fixed
-  int64_t* dr = out_.as<int64_t>();
-  float* ds = reinterpret_cast<float*>(dr + n);
-  uint32_t* dfx = reinterpret_cast<uint32_t*>(ds + n);
+  int64_t* dr;
+  float* ds;
+  uint32_t* dfx;
+  Carve c;
+  c.part(n, &dr, &ds, &dfx);
+  out_.carve(c);
   begin(stream_);
   SR_HIP(hipMemcpyAsync(dr, rows, n * 8, hipMemcpyHostToDevice, stream_));
   end(stream_);

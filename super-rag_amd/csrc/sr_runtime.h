@@ -11,6 +11,7 @@
 #include <fcntl.h>
 #include <unistd.h>
 
+#include "sr_carve.h"
 #include "sr_common.h"
 
 namespace sr {
@@ -48,10 +49,26 @@ struct DevBuf {
     SR_HIP(hipMalloc(&p, n));
     bytes = n;
   }
+  // Grow to the carver's total and point its parts into the buffer (sr_carve.h).
+  void carve(const Carve& c) { reserve(c.bytes()); c.bind(p); }
   template <class T>
   T* as() const {
     return reinterpret_cast<T*>(p);
   }
+};
+
+// A non-blocking stream of the current device for the length of one call: synchronised and
+// destroyed on every way out of the scope, an exception included (errors of either are ignored).
+struct ScopedStream {
+  hipStream_t s = nullptr;
+  ScopedStream() { SR_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
+  ScopedStream(const ScopedStream&) = delete;
+  ScopedStream& operator=(const ScopedStream&) = delete;
+  ~ScopedStream() {
+    (void)hipStreamSynchronize(s);
+    (void)hipStreamDestroy(s);
+  }
+  operator hipStream_t() const { return s; }
 };
 
 // Scoped device selection (restores the caller's current device).
@@ -155,7 +172,7 @@ class Store {
   hipStream_t stream_ = nullptr;
   hipEvent_t done_ = nullptr;
   // search workspace
-  DevBuf qbuf_, qstage_, cand_, cnt_, tau_, overflow_, osim_, orows_, scratch_;
+  DevBuf qbuf_, qstage_, cand_, cnt_, tau_, overflow_, scratch_;
   int ws_queries_ = 0;
   // fp8 scan: e4m3(256 x) copy of the rows (ld8 bytes each), query staging, fp8-stage candidates
   bool fp8_ = false;

@@ -43,6 +43,11 @@ constexpr int kDenseRows = 8192;
 constexpr int kQueryBlock = 256;
 constexpr int64_t kAddChunk = 1 << 16;
 
+// What the host searches report: 1 - sim of the rows found, +inf in the slots without a row.
+void sims_to_distances(float* sim, const int64_t* rows, size_t n) {
+  for (size_t i = 0; i < n; ++i) sim[i] = rows[i] >= 0 ? 1.0f - sim[i] : INFINITY;
+}
+
 __global__ void clear_flags_kernel(uint8_t* live, const int64_t* rows, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) live[rows[i]] = 0;
@@ -249,9 +254,12 @@ void Store::get(const int64_t* rows, int64_t n, float* out) {
   DeviceGuard g(device_);
   begin(stream_);
   SR_HIP(hipStreamSynchronize(stream_));
-  scratch_.reserve((size_t)n * (sizeof(int64_t) + dim_ * sizeof(float)));
-  int64_t* drows = scratch_.as<int64_t>();
-  float* dout = reinterpret_cast<float*>(drows + n);
+  int64_t* drows;
+  float* dout;
+  Carve c;
+  c.part((size_t)n, &drows);
+  c.part((size_t)n * dim_, &dout);
+  scratch_.carve(c);
   SR_HIP(hipMemcpyAsync(drows, rows, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, stream_));
   hipLaunchKernelGGL(f16_to_f32_rows_kernel, dim3((unsigned)n), dim3(256), 0, stream_,
                      corpus_.as<half_t>(), ld_, drows, n, dim_, dout);
@@ -433,20 +441,19 @@ void Store::search_host(const float* q, int B, int k, float* out_dist, int64_t* 
   if (B == 0) return;
   DeviceGuard g(device_);
   const uint8_t* elig = eligibility(allow, mask_key);
-  const size_t qb = (size_t)B * dim_ * sizeof(float);
-  const size_t ob = (size_t)B * k * (sizeof(float) + sizeof(int64_t));
-  qstage_.reserve(qb + ob);
-  float* dq = qstage_.as<float>();
-  float* dsim = reinterpret_cast<float*>(qstage_.as<char>() + qb);
-  int64_t* drows = reinterpret_cast<int64_t*>(dsim + (size_t)B * k);
-  SR_HIP(hipMemcpyAsync(dq, q, qb, hipMemcpyHostToDevice, stream_));
+  const size_t nq = (size_t)B * dim_, nk = (size_t)B * k;
+  float *dq, *dsim;
+  int64_t* drows;
+  Carve c;
+  c.part(nq, &dq);
+  c.part(nk, &dsim, &drows);
+  qstage_.carve(c);
+  SR_HIP(hipMemcpyAsync(dq, q, nq * sizeof(float), hipMemcpyHostToDevice, stream_));
   search_dev(dq, SR_DTYPE_F32, B, k, dsim, drows, 0, stream_, elig);
-  SR_HIP(hipMemcpyAsync(out_dist, dsim, (size_t)B * k * sizeof(float), hipMemcpyDeviceToHost, stream_));
-  SR_HIP(hipMemcpyAsync(out_rows, drows, (size_t)B * k * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
+  SR_HIP(hipMemcpyAsync(out_dist, dsim, nk * sizeof(float), hipMemcpyDeviceToHost, stream_));
+  SR_HIP(hipMemcpyAsync(out_rows, drows, nk * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
   SR_HIP(hipStreamSynchronize(stream_));
-  if (raw_sim) return;
-  for (int64_t i = 0; i < (int64_t)B * k; ++i)
-    out_dist[i] = out_rows[i] >= 0 ? 1.0f - out_dist[i] : INFINITY;
+  if (!raw_sim) sims_to_distances(out_dist, out_rows, nk);
 }
 
 // Subset search: every query scores only the rows of its own list (k_subset.hip), then K2.  Per
@@ -550,23 +557,28 @@ void Store::search_subset_host(const float* q, int B, int k, const int32_t* q_li
   DeviceGuard g(device_);
   begin(stream_);
   ensure_query_ws(B);
-  const size_t off_bytes = (size_t)(n_lists + 1) * sizeof(int64_t);
-  const size_t row_bytes = (size_t)total * sizeof(int64_t);
-  subset_.reserve(off_bytes + row_bytes + meta.size() * sizeof(int32_t));
-  int64_t* d_off = subset_.as<int64_t>();
-  int64_t* d_rows = d_off + (n_lists + 1);
-  int32_t* d_meta = reinterpret_cast<int32_t*>(d_rows + total);
-  SR_HIP(hipMemcpyAsync(d_off, list_off, off_bytes, hipMemcpyHostToDevice, stream_));
+  int64_t *d_off, *d_rows;
+  int32_t* d_meta;
+  Carve cs;
+  cs.part((size_t)n_lists + 1, &d_off);
+  cs.part((size_t)total, &d_rows);
+  cs.part(meta.size(), &d_meta);
+  subset_.carve(cs);
+  SR_HIP(hipMemcpyAsync(d_off, list_off, ((size_t)n_lists + 1) * sizeof(int64_t), hipMemcpyHostToDevice,
+                        stream_));
   if (total > 0)
-    SR_HIP(hipMemcpyAsync(d_rows, list_rows, row_bytes, hipMemcpyHostToDevice, stream_));
+    SR_HIP(hipMemcpyAsync(d_rows, list_rows, (size_t)total * sizeof(int64_t), hipMemcpyHostToDevice,
+                          stream_));
   SR_HIP(hipMemcpyAsync(d_meta, meta.data(), meta.size() * sizeof(int32_t), hipMemcpyHostToDevice,
                         stream_));
-  const size_t qb = (size_t)B * dim_ * sizeof(float);
-  qstage_.reserve(qb + (size_t)B * k * (sizeof(float) + sizeof(int64_t)));
-  float* dq = qstage_.as<float>();
-  float* dsim = reinterpret_cast<float*>(qstage_.as<char>() + qb);
-  int64_t* drows = reinterpret_cast<int64_t*>(dsim + (size_t)B * k);
-  SR_HIP(hipMemcpyAsync(dq, q, qb, hipMemcpyHostToDevice, stream_));
+  const size_t nq = (size_t)B * dim_, nk = (size_t)B * k;
+  float *dq, *dsim;
+  int64_t* drows;
+  Carve c;
+  c.part(nq, &dq);
+  c.part(nk, &dsim, &drows);
+  qstage_.carve(c);
+  SR_HIP(hipMemcpyAsync(dq, q, nq * sizeof(float), hipMemcpyHostToDevice, stream_));
   half_t* qn = qbuf_.as<half_t>();
   launch_normalize_rows(dq, SR_DTYPE_F32, B, dim_, qn, ld_, stream_);
   SR_HIP(hipMemsetAsync(overflow_.p, 0, sizeof(int), stream_));
@@ -615,16 +627,14 @@ void Store::search_mmr_host(const float* q, int B, int k, int k_cand, float lamb
   if (B == 0) return;
   DeviceGuard g(device_);
   const uint8_t* elig = eligibility(allow, mask_key);
-  // staging: queries | candidate rows | kept rows | candidate sims | kept score | kept sim
-  const size_t qb = (size_t)round_up((int64_t)B * dim_ * sizeof(float), 16);
   const size_t nc = (size_t)B * k_cand, nk = (size_t)B * k;
-  qstage_.reserve(qb + nc * 12 + nk * 16);
-  float* dq = qstage_.as<float>();
-  int64_t* crows = reinterpret_cast<int64_t*>(qstage_.as<char>() + qb);
-  int64_t* drows = crows + nc;
-  float* csim = reinterpret_cast<float*>(drows + nk);
-  float* dscore = csim + nc;
-  float* dsim = dscore + nk;
+  float *dq, *csim, *dscore, *dsim;
+  int64_t *crows, *drows;
+  Carve c;
+  c.part((size_t)B * dim_, &dq);
+  c.part(nc, &crows, &csim);           // the candidates of the scan
+  c.part(nk, &drows, &dscore, &dsim);  // what MMR keeps of them
+  qstage_.carve(c);
   SR_HIP(hipMemcpyAsync(dq, q, (size_t)B * dim_ * sizeof(float), hipMemcpyHostToDevice, stream_));
   search_dev(dq, SR_DTYPE_F32, B, k_cand, csim, crows, 0, stream_, elig);
   mmr_dev(crows, csim, B, k_cand, 0, lambda, mode, min_score, k, dscore, dsim, drows, stream_);
@@ -632,7 +642,7 @@ void Store::search_mmr_host(const float* q, int B, int k, int k_cand, float lamb
   SR_HIP(hipMemcpyAsync(out_dist, dsim, nk * sizeof(float), hipMemcpyDeviceToHost, stream_));
   SR_HIP(hipMemcpyAsync(out_rows, drows, nk * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
   SR_HIP(hipStreamSynchronize(stream_));
-  for (size_t i = 0; i < nk; ++i) out_dist[i] = out_rows[i] >= 0 ? 1.0f - out_dist[i] : INFINITY;
+  sims_to_distances(out_dist, out_rows, nk);
 }
 
 const int32_t* Store::group_array(const int32_t* group, int64_t group_key) {
@@ -665,13 +675,15 @@ void Store::group_dev(const int64_t* cand_rows, const float* cand_sims, int B, i
            "store.group: null buffer");
   DeviceGuard g(device_);
   const int32_t* dg = group_array(group, group_key);
-  // per-query state the continuation of search_grouped_host would read: found list | n_groups
-  const size_t nk = (size_t)B * k;
-  if (gstate_.bytes < nk * sizeof(uint64_t) + (size_t)B * sizeof(int32_t))
+  // per-query state the continuation of search_grouped_host would read: found list, n_groups
+  uint64_t* found;
+  int32_t* ng;
+  Carve c;
+  c.part((size_t)B * k, &found);
+  c.part((size_t)B, &ng);
+  if (gstate_.bytes < c.bytes())
     SR_HIP(hipEventSynchronize(done_));  // an earlier collapse may still write the old buffer
-  gstate_.reserve(nk * sizeof(uint64_t) + (size_t)B * sizeof(int32_t));
-  uint64_t* found = gstate_.as<uint64_t>();
-  int32_t* ng = reinterpret_cast<int32_t*>(found + nk);
+  gstate_.carve(c);
   begin(s);
   launch_group_collapse(cand_sims, cand_rows, B, K, nullptr, nullptr, 0, row_offset, dg, n_rows_, k,
                         group_size, out_sim, out_rows, out_group, ng, out_complete, found, nullptr,
@@ -690,23 +702,21 @@ void Store::search_grouped_host(const float* q, int B, int k, int group_size, in
   DeviceGuard g(device_);
   const int32_t* dg = group_array(group, group_key);
   const uint8_t* elig = eligibility(allow, mask_key);
-  // staging: queries | candidate rows | kept rows | carried rows x 2 | found lists | candidate sims |
-  // kept sims | carried sims x 2 | group ids | n_groups | complete
   const size_t kg = (size_t)k * group_size;
   const size_t nc = (size_t)B * k_cand, no = (size_t)B * kg, nk = (size_t)B * k;
-  const size_t qb = (size_t)round_up((int64_t)B * dim_ * sizeof(float), 16);
-  gstage_.reserve(qb + nc * 12 + no * 36 + nk * 12 + (size_t)B * 8);
-  float* dq = gstage_.as<float>();
-  int64_t* crows = reinterpret_cast<int64_t*>(gstage_.as<char>() + qb);
-  int64_t* orows = crows + nc;
-  int64_t* nrows[2] = {orows + no, orows + 2 * no};
-  uint64_t* found = reinterpret_cast<uint64_t*>(orows + 3 * no);
-  float* csim = reinterpret_cast<float*>(found + nk);
-  float* osim = csim + nc;
-  float* nsim[2] = {osim + no, osim + 2 * no};
-  int32_t* ogrp = reinterpret_cast<int32_t*>(osim + 3 * no);
-  int32_t* ng = ogrp + nk;
-  int32_t* comp = ng + B;
+  float *dq, *csim, *osim, *nsim[2];
+  int64_t *crows, *orows, *nrows[2];
+  uint64_t* found;
+  int32_t *ogrp, *ng, *comp;
+  Carve c;
+  c.part((size_t)B * dim_, &dq);
+  c.part(nc, &crows, &csim);  // the candidates of a round
+  c.part(no, &orows, &osim);  // the kept rows of the kept groups
+  // the rows of full groups carried into the next round, in and out
+  c.part(no, &nrows[0], &nsim[0], &nrows[1], &nsim[1]);
+  c.part(nk, &found, &ogrp);  // per query: the found list, the kept group ids, n_groups, complete
+  c.part((size_t)B, &ng, &comp);
+  gstage_.carve(c);
 
   // round 0: the whole batch
   SR_HIP(hipMemcpyAsync(dq, q, (size_t)B * dim_ * sizeof(float), hipMemcpyHostToDevice, stream_));
@@ -787,12 +797,13 @@ void Store::score_rows_host(const float* q, int B, const int64_t* rows, int K, f
   if (B == 0 || K == 0) return;
   SR_CHECK(q && rows && out_sim, "store.score_rows: null buffer");
   DeviceGuard g(device_);
-  const size_t qb = (size_t)round_up((int64_t)B * dim_ * sizeof(float), 16);
   const size_t nk = (size_t)B * K;
-  qstage_.reserve(qb + nk * (sizeof(int64_t) + sizeof(float)));
-  float* dq = qstage_.as<float>();
-  int64_t* drows = reinterpret_cast<int64_t*>(qstage_.as<char>() + qb);
-  float* dsim = reinterpret_cast<float*>(drows + nk);
+  float *dq, *dsim;
+  int64_t* drows;
+  Carve c;
+  c.part((size_t)B * dim_, &dq);
+  c.part(nk, &drows, &dsim);
+  qstage_.carve(c);
   SR_HIP(hipMemcpyAsync(dq, q, (size_t)B * dim_ * sizeof(float), hipMemcpyHostToDevice, stream_));
   SR_HIP(hipMemcpyAsync(drows, rows, nk * sizeof(int64_t), hipMemcpyHostToDevice, stream_));
   score_rows_dev(dq, SR_DTYPE_F32, B, drows, K, 0, dsim, stream_);
