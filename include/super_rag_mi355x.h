@@ -353,6 +353,56 @@ int sr_lex_load(const char* path, int device, sr_lex** out);
 int sr_lex_compact(sr_lex* x, int64_t* old_to_new);
 void sr_lex_destroy(sr_lex* x);
 
+/* ------------------------------------------------------------------------------------------------
+ * Learned-sparse retrieval: the impact scoring mode of sr_lex (k_lex.hip; DESIGN.md "Learned-sparse
+ * retrieval").  An sr_lex created by sr_lex_create_impact holds, per posting, an fp32 document
+ * weight where a BM25 index holds tf (bge-m3's sparse head, SPLADE, a "sparse vector" of Qdrant /
+ * Milvus), and a query is term ids WITH weights.  Scoring, exact and order-independent: for every
+ * posting of a scored term t in a live eligible row, p = fl32(qw_t * dw) (one fp32 multiply),
+ * fixed = max(1, rint(p * 65536)) as uint32; a row's score is the integer sum out_fixed over those
+ * postings (a row carrying t in two postings sums both) and out_score = (float)out_fixed / 65536.
+ * It differs from the fp64 dot product by at most n_shared (2^-16 + p 2^-24) per row.
+ * Limits, all SR_ERR_INVALID on the host before any device work: document weights finite and in
+ * (0, SR_IMPACT_MAX_WEIGHT]; query weights finite and >= 0; a query whose distinct term ids (known
+ * to the index or not) give sum_t (16 * qw_t * 65536 + 1) >= 2^32, in double, is rejected, so no
+ * row's uint32 sum of distinct terms can overflow.  Query preparation: a zero-weight term is
+ * dropped, a term id repeated in one query keeps its MAXIMUM weight (bge-m3's rule), ids < 0, >=
+ * the vocabulary or with no live posting are ignored.
+ * sr_lex_remove / _stats (avgdl reported as 0) / _compact / _save / _load / _destroy work on both
+ * modes; an impact snapshot has the magic "SRMILEX2" and the layout of "SRMILEX1" with the weight's
+ * bits in tf's place (the loader checks the weight range as it checks tf) and sr_lex_load restores
+ * the mode.  Every BM25 entry point (sr_lex_add, sr_lex_search*, sr_lex_score_rows*, sr_lex_df,
+ * sr_lex_totals, sr_lex_query_stats_dev, sr_hybrid_search*) returns SR_ERR_STATE on an impact index,
+ * and every *_weighted entry point returns SR_ERR_STATE on a BM25 index.
+ * Not provided: *_dev variants, corpus-global statistics (the score needs none, so per-shard lists
+ * of a row-sharded corpus merge as they are), ShardedLex / sr_store_set_* counterparts, a connector
+ * ctx switch, and a fused C entry point (lexical.sparse_hybrid_search composes the existing ones).
+ * ---------------------------------------------------------------------------------------------- */
+#define SR_LEX_BM25 0
+#define SR_LEX_IMPACT 1
+#define SR_IMPACT_MAX_WEIGHT 16.0f
+
+int sr_lex_create_impact(int device, sr_lex** out);
+/* out_mode = SR_LEX_BM25 or SR_LEX_IMPACT. */
+int sr_lex_scoring(sr_lex* x, int* out_mode);
+/* Append n documents: document i has the DISTINCT term ids terms[off[i] .. off[i+1]) with weights
+ * weights[...]; off[0] == 0; first_row as in sr_lex_add. */
+int sr_lex_add_weighted(sr_lex* x, const int64_t* off, const int32_t* terms, const float* weights,
+                        int64_t n, int64_t* first_row);
+/* Impact top-k: query b is the term ids qterms[qoff[b] .. qoff[b+1]) with weights qweights[...].
+ * Outputs, order, allow and mask_key as in sr_lex_search; out_fixed (optional, B x k uint32) the exact
+ * fixed-point scores, 0 past the matches.  Host buffers, blocking. */
+int sr_lex_search_weighted(sr_lex* x, const int64_t* qoff, const int32_t* qterms,
+                           const float* qweights, int B, int k, const uint8_t* allow,
+                           int64_t mask_key, float* out_score, int64_t* out_rows,
+                           uint32_t* out_fixed);
+/* Exact impact score of given (query, row) pairs, as sr_lex_score_rows: -inf / 0 for a row < 0, >=
+ * n_rows or tombstoned (checked before anything is indexed by it), 0.0f / 0 for a live row sharing
+ * no scored term, else sr_lex_search_weighted's value for the same pair bit for bit. */
+int sr_lex_score_rows_weighted(sr_lex* x, const int64_t* qoff, const int32_t* qterms,
+                               const float* qweights, int B, const int64_t* rows, int K,
+                               float* out_score, uint32_t* out_fixed);
+
 /* Reciprocal-rank fusion of two ranked row lists per query (B x ka and B x kb, -1 padded), as
  * graphiti rrf (graphiti_core/search/search_utils.py:1762-1778): score = sum 1 / (rank +
  * rank_const) in fp64, order (score desc, first appearance), rows with score < min_score
@@ -505,6 +555,43 @@ int sr_encoder_forward(sr_encoder* e, const int32_t* ids, const int32_t* mask,
 int sr_encoder_forward_dev(sr_encoder* e, const int32_t* ids, const int32_t* mask,
                            const int32_t* type_ids, int B, int S, int pool, void* out,
                            int out_dtype, int ld_out, void* stream);
+/* The sparse head of a multi-function embedder (bge-m3's sparse_linear; k_encoder_misc.hip,
+ * DESIGN.md "Learned-sparse retrieval").  sr_encoder_set_weight accepts "sparse_linear.weight"
+ * (hidden values) and "sparse_linear.bias" (1 value), kept fp32.  They are optional:
+ * sr_encoder_ready and every other call behave the same with or without them, and the calls
+ * below return SR_ERR_STATE until both are set.
+ *   token weight   tw[b, s] = max(0, sum_i h[b, s, i] w[i] + bias) where mask[b, s] != 0, else 0,
+ *                  h the final state of the token (fp32 accumulation);
+ *   term collapse  a position qualifies when mask != 0, tw > 0 and ids[b, s] is none of special_ids;
+ *                  each distinct qualifying id is emitted once, with the MAXIMUM tw over its
+ *                  qualifying positions, in ascending order of its first qualifying position
+ *                  (bge-m3's _process_token_weights): out_terms[b, 0 .. out_count[b]) and
+ *                  out_weights likewise; the slots past the count hold -1 / 0.  Exact.
+ * sr_sparse_terms_dev is the collapse alone, on any token weights (no encoder needed): ids / mask /
+ * tok_weight B x S device, special_ids host with n_special in [0, 16], outputs B x S / B x S / B
+ * device; S in [1, 8192]; asynchronous on `stream` of `device`.  B == 0 is a no-op; a shape outside
+ * these limits or a null buffer is SR_ERR_INVALID before any device call.
+ * sr_encoder_forward_sparse_dev is ONE forward pass giving the dense embedding (out_dense /
+ * out_dtype / ld_out as in sr_encoder_forward_dev) and the sparse outputs (device; out_tok_weight B x
+ * S may be NULL).  The last layer runs for every token whatever the pooling, so with SR_POOL_MEAN the
+ * dense output equals sr_encoder_forward_dev's bit for bit, and with SR_POOL_CLS it comes from a full
+ * last layer where sr_encoder_forward_dev computes the CLS rows only (the same values within
+ * rounding).  sr_encoder_forward_sparse takes and fills host buffers (out_dense B x hidden fp32) and
+ * blocks.
+ * Not provided: an fp16 / packed output of the terms, a sparse head on a cross-encoder
+ * (classifier models), and sequences longer than 8192 tokens. */
+int sr_sparse_terms_dev(const int32_t* ids, const int32_t* mask, const float* tok_weight, int B, int S,
+                        const int32_t* special_ids, int n_special, int32_t* out_terms,
+                        float* out_weights, int32_t* out_count, int device, void* stream);
+int sr_encoder_forward_sparse_dev(sr_encoder* e, const int32_t* ids, const int32_t* mask,
+                                  const int32_t* type_ids, int B, int S, int pool, void* out_dense,
+                                  int out_dtype, int ld_out, const int32_t* special_ids, int n_special,
+                                  float* out_tok_weight, int32_t* out_terms, float* out_weights,
+                                  int32_t* out_count, void* stream);
+int sr_encoder_forward_sparse(sr_encoder* e, const int32_t* ids, const int32_t* mask,
+                              const int32_t* type_ids, int B, int S, int pool, float* out_dense,
+                              const int32_t* special_ids, int n_special, float* out_tok_weight,
+                              int32_t* out_terms, float* out_weights, int32_t* out_count);
 /* Cross-encoder relevance: P (query, passage) pairs already packed as token ids (P x S);
  * out_logits: P x num_labels fp32 raw logits (bge-reranker scores = logits, sigmoid optional). */
 int sr_cross_score(sr_encoder* e, const int32_t* ids, const int32_t* mask,

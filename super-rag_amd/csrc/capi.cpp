@@ -117,6 +117,14 @@ ProfScope::~ProfScope() {
     return SR_ERR_INVALID;                   \
   }
 
+// The scoring mode an entry point needs (SR_LEX_BM25 / SR_LEX_IMPACT): SR_ERR_STATE on the other.
+static void lex_need_mode(const sr_lex* x, int mode, const char* who) {
+  if (x->impl->mode() != mode)
+    throw sr::Error(SR_ERR_STATE, std::string(who) + (mode == SR_LEX_IMPACT
+                                                          ? ": needs an impact index (sr_lex_create_impact)"
+                                                          : ": needs a BM25 index, this one scores impacts"));
+}
+
 #define SR_NONNULL(p)                                                   \
   do {                                                                  \
     if (!(p)) throw sr::Error(SR_ERR_INVALID, "null argument: " #p);    \
@@ -513,10 +521,79 @@ int sr_lex_create(int device, float k1, float b, sr_lex** out) {
   SR_API_END
 }
 
+int sr_lex_create_impact(int device, sr_lex** out) {
+  SR_API_BEGIN
+  SR_NONNULL(out);
+  *out = nullptr;
+  *out = new sr_lex{new sr::LexIndex(device, 0.f, 0.f, SR_LEX_IMPACT)};
+  SR_API_END
+}
+
+int sr_lex_scoring(sr_lex* x, int* out_mode) {
+  SR_API_BEGIN
+  SR_NONNULL(x);
+  SR_NONNULL(out_mode);
+  *out_mode = x->impl->mode();
+  SR_API_END
+}
+
+int sr_lex_add_weighted(sr_lex* x, const int64_t* off, const int32_t* terms, const float* weights,
+                        int64_t n, int64_t* first_row) {
+  SR_API_BEGIN
+  SR_NONNULL(x);
+  lex_need_mode(x, SR_LEX_IMPACT, "sr_lex_add_weighted");
+  std::lock_guard<std::mutex> lk(x->impl->mu);
+  x->impl->add_weighted(off, terms, weights, n, first_row);
+  SR_API_END
+}
+
+int sr_lex_search_weighted(sr_lex* x, const int64_t* qoff, const int32_t* qterms,
+                           const float* qweights, int B, int k, const uint8_t* allow,
+                           int64_t mask_key, float* out_score, int64_t* out_rows,
+                           uint32_t* out_fixed) {
+  SR_API_BEGIN
+  SR_NONNULL(x);
+  lex_need_mode(x, SR_LEX_IMPACT, "sr_lex_search_weighted");
+  if (B > 0) {
+    SR_NONNULL(qoff);
+    SR_NONNULL(out_score);
+    SR_NONNULL(out_rows);
+    if (qoff[B] > 0) {
+      SR_NONNULL(qterms);
+      SR_NONNULL(qweights);
+    }
+  }
+  std::lock_guard<std::mutex> lk(x->impl->mu);
+  x->impl->search_weighted_host(qoff, qterms, qweights, B, k, allow, mask_key, out_score, out_rows,
+                                out_fixed);
+  SR_API_END
+}
+
+int sr_lex_score_rows_weighted(sr_lex* x, const int64_t* qoff, const int32_t* qterms,
+                               const float* qweights, int B, const int64_t* rows, int K,
+                               float* out_score, uint32_t* out_fixed) {
+  SR_API_BEGIN
+  SR_CHECK(B >= 0 && K >= 0, "lex.score_rows: negative shape");
+  SR_NONNULL(x);
+  lex_need_mode(x, SR_LEX_IMPACT, "sr_lex_score_rows_weighted");
+  if (B == 0 || K == 0) return SR_OK;
+  SR_NONNULL(qoff);
+  SR_NONNULL(rows);
+  SR_NONNULL(out_score);
+  if (qoff[B] > 0) {
+    SR_NONNULL(qterms);
+    SR_NONNULL(qweights);
+  }
+  std::lock_guard<std::mutex> lk(x->impl->mu);
+  x->impl->score_rows_weighted_host(qoff, qterms, qweights, B, rows, K, out_score, out_fixed);
+  SR_API_END
+}
+
 int sr_lex_add(sr_lex* x, const int64_t* off, const int32_t* terms, const int32_t* tf,
                const int32_t* dl, int64_t n, int64_t* first_row) {
   SR_API_BEGIN
   SR_NONNULL(x);
+  lex_need_mode(x, SR_LEX_BM25, "sr_lex_add");
   std::lock_guard<std::mutex> lk(x->impl->mu);
   x->impl->add(off, terms, tf, dl, n, first_row);
   SR_API_END
@@ -544,6 +621,7 @@ int sr_lex_search(sr_lex* x, const int64_t* qoff, const int32_t* qterms, int B, 
                   const uint8_t* allow, int64_t mask_key, float* out_score, int64_t* out_rows) {
   SR_API_BEGIN
   SR_NONNULL(x);
+  lex_need_mode(x, SR_LEX_BM25, "sr_lex_search");
   if (B > 0) {
     SR_NONNULL(qoff);
     SR_NONNULL(out_score);
@@ -560,6 +638,7 @@ int sr_lex_search_global(sr_lex* x, const int64_t* qoff, const int32_t* qterms, 
                          float* out_score, int64_t* out_rows) {
   SR_API_BEGIN
   SR_NONNULL(x);
+  lex_need_mode(x, SR_LEX_BM25, "sr_lex_search_global");
   if (B > 0) {
     SR_NONNULL(qoff);
     SR_NONNULL(out_score);
@@ -576,6 +655,7 @@ int sr_lex_search_global_fixed(sr_lex* x, const int64_t* qoff, const int32_t* qt
                                float* out_score, int64_t* out_rows, uint32_t* out_fixed) {
   SR_API_BEGIN
   SR_NONNULL(x);
+  lex_need_mode(x, SR_LEX_BM25, "sr_lex_search_global_fixed");
   if (B > 0) {
     SR_NONNULL(qoff);
     SR_NONNULL(out_score);
@@ -591,6 +671,7 @@ int sr_lex_search_global_fixed(sr_lex* x, const int64_t* qoff, const int32_t* qt
 int sr_lex_totals(sr_lex* x, int64_t* n_live, int64_t* sum_dl) {
   SR_API_BEGIN
   SR_NONNULL(x);
+  lex_need_mode(x, SR_LEX_BM25, "sr_lex_totals");
   std::lock_guard<std::mutex> lk(x->impl->mu);
   x->impl->totals(n_live, sum_dl);
   SR_API_END
@@ -599,6 +680,7 @@ int sr_lex_totals(sr_lex* x, int64_t* n_live, int64_t* sum_dl) {
 int sr_lex_df(sr_lex* x, const int32_t* terms, int n, int64_t* out_df) {
   SR_API_BEGIN
   SR_NONNULL(x);
+  lex_need_mode(x, SR_LEX_BM25, "sr_lex_df");
   SR_CHECK(n >= 0, "lex.df: negative count");
   if (n > 0) {
     SR_NONNULL(terms);
@@ -614,6 +696,7 @@ int sr_lex_search_dev(sr_lex* x, const int64_t* qoff, const int32_t* qterms, int
                       int64_t row_offset, void* stream) {
   SR_API_BEGIN
   SR_NONNULL(x);
+  lex_need_mode(x, SR_LEX_BM25, "sr_lex_search_dev");
   if (B > 0) {
     SR_NONNULL(qoff);
     SR_NONNULL(out_score);
@@ -630,6 +713,7 @@ int sr_lex_query_stats_dev(sr_lex* x, const int32_t* tok, const int32_t* qlen, i
                            int64_t* out_stats, void* stream) {
   SR_API_BEGIN
   SR_NONNULL(x);
+  lex_need_mode(x, SR_LEX_BM25, "sr_lex_query_stats_dev");
   SR_NONNULL(out_stats);
   SR_CHECK(B >= 0 && Lq >= 0, "lex.query_stats: negative shape");
   if ((int64_t)B * Lq > 0) {
@@ -646,6 +730,7 @@ int sr_lex_search_tok_dev(sr_lex* x, const int32_t* tok, const int32_t* qlen, in
                           int64_t row_offset, void* stream) {
   SR_API_BEGIN
   SR_NONNULL(x);
+  lex_need_mode(x, SR_LEX_BM25, "sr_lex_search_tok_dev");
   if (B > 0) {
     SR_NONNULL(qlen);
     SR_NONNULL(out_score);
@@ -664,6 +749,7 @@ int sr_lex_score_rows(sr_lex* x, const int64_t* qoff, const int32_t* qterms, int
   SR_API_BEGIN
   SR_CHECK(B >= 0 && K >= 0, "lex.score_rows: negative shape");
   SR_NONNULL(x);
+  lex_need_mode(x, SR_LEX_BM25, "sr_lex_score_rows");
   if (B == 0 || K == 0) return SR_OK;
   SR_NONNULL(qoff);
   SR_NONNULL(rows);
@@ -679,6 +765,7 @@ int sr_lex_score_rows_dev(sr_lex* x, const int64_t* qoff, const int32_t* qterms,
   SR_API_BEGIN
   SR_CHECK(B >= 0 && K >= 0, "lex.score_rows: negative shape");
   SR_NONNULL(x);
+  lex_need_mode(x, SR_LEX_BM25, "sr_lex_score_rows_dev");
   if (B == 0 || K == 0) return SR_OK;
   SR_NONNULL(qoff);
   SR_NONNULL(rows);
@@ -773,6 +860,7 @@ int sr_hybrid_search(sr_store* s, sr_lex* x, const float* q, const int64_t* qoff
   SR_API_BEGIN
   SR_NONNULL(s);
   SR_NONNULL(x);
+  lex_need_mode(x, SR_LEX_BM25, "sr_hybrid_search");
   SR_CHECK(B >= 0, "hybrid: negative batch");
   if (B == 0) return SR_OK;
   SR_NONNULL(q);
@@ -945,6 +1033,7 @@ int sr_hybrid_search_fused(sr_store* s, sr_lex* x, const float* q, const int64_t
   sr::fuse_check_args(B, k_each, k_each, mode, alpha, k, /*allow_full=*/true);
   SR_NONNULL(s);
   SR_NONNULL(x);
+  lex_need_mode(x, SR_LEX_BM25, "sr_hybrid_search_fused");
   if (B == 0) return SR_OK;
   SR_NONNULL(q);
   SR_NONNULL(qoff);
@@ -1041,6 +1130,61 @@ int sr_encoder_forward_dev(sr_encoder* e, const int32_t* ids, const int32_t* mas
   std::lock_guard<std::mutex> lk(e->impl->mu);
   e->impl->forward_dev(ids, mask, type_ids, B, S, 0, pool, out, out_dtype, ld_out,
                        reinterpret_cast<hipStream_t>(stream));
+  SR_API_END
+}
+
+int sr_sparse_terms_dev(const int32_t* ids, const int32_t* mask, const float* tok_weight, int B, int S,
+                        const int32_t* special_ids, int n_special, int32_t* out_terms,
+                        float* out_weights, int32_t* out_count, int device, void* stream) {
+  SR_API_BEGIN
+  sr::sparse_terms_check_args(B, S, n_special);
+  if (n_special > 0) SR_NONNULL(special_ids);
+  if (B == 0) return SR_OK;
+  SR_NONNULL(ids);
+  SR_NONNULL(mask);
+  SR_NONNULL(tok_weight);
+  SR_NONNULL(out_terms);
+  SR_NONNULL(out_weights);
+  SR_NONNULL(out_count);
+  sr::DeviceGuard g(device);
+  sr::launch_sparse_terms(ids, mask, tok_weight, B, S, special_ids, n_special, out_terms, out_weights,
+                          out_count, reinterpret_cast<hipStream_t>(stream));
+  SR_API_END
+}
+
+int sr_encoder_forward_sparse_dev(sr_encoder* e, const int32_t* ids, const int32_t* mask,
+                                  const int32_t* type_ids, int B, int S, int pool, void* out_dense,
+                                  int out_dtype, int ld_out, const int32_t* special_ids, int n_special,
+                                  float* out_tok_weight, int32_t* out_terms, float* out_weights,
+                                  int32_t* out_count, void* stream) {
+  SR_API_BEGIN
+  SR_NONNULL(e);
+  if (B > 0) {
+    SR_NONNULL(ids);
+    SR_NONNULL(mask);
+    SR_NONNULL(out_dense);
+    SR_NONNULL(out_terms);
+    SR_NONNULL(out_weights);
+    SR_NONNULL(out_count);
+  }
+  if (n_special > 0) SR_NONNULL(special_ids);
+  std::lock_guard<std::mutex> lk(e->impl->mu);
+  const sr::Encoder::SparseOut so{special_ids, n_special, out_tok_weight, out_terms, out_weights, out_count};
+  e->impl->forward_dev(ids, mask, type_ids, B, S, 0, pool, out_dense, out_dtype, ld_out,
+                       reinterpret_cast<hipStream_t>(stream), &so);
+  SR_API_END
+}
+
+int sr_encoder_forward_sparse(sr_encoder* e, const int32_t* ids, const int32_t* mask,
+                              const int32_t* type_ids, int B, int S, int pool, float* out_dense,
+                              const int32_t* special_ids, int n_special, float* out_tok_weight,
+                              int32_t* out_terms, float* out_weights, int32_t* out_count) {
+  SR_API_BEGIN
+  SR_NONNULL(e);
+  if (n_special > 0) SR_NONNULL(special_ids);
+  std::lock_guard<std::mutex> lk(e->impl->mu);
+  e->impl->forward_sparse_host(ids, mask, type_ids, B, S, pool, out_dense, special_ids, n_special,
+                               out_tok_weight, out_terms, out_weights, out_count);
   SR_API_END
 }
 

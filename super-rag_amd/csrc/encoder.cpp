@@ -15,6 +15,8 @@
 // classification head the last layer is computed for the CLS rows only.
 // Embedding mode pools (CLS / masked mean) and L2-normalises (K7); cross-encoder mode applies the
 // RoBERTa classification head: tanh(GEMM(h16[CLS rows], Wc) + bc) (fp32) . Wout + bout (K4 + K8).
+// With a sparse-head request (forward_dev's SparseOut) the last layer runs for every token and the
+// final states also feed sparse_token_weights and sparse_terms (k_encoder_misc.hip), per chunk.
 #include <algorithm>
 #include <cstdlib>
 #include <vector>
@@ -128,6 +130,22 @@ void Encoder::register_target(const std::string& name, DevBuf& buf, int64_t nume
 }
 
 void Encoder::set_weight(const std::string& name, const float* data, int64_t numel) {
+  if (name == "sparse_linear.weight" || name == "sparse_linear.bias") {
+    // the optional sparse head, kept fp32; never part of missing() / sr_encoder_ready
+    const bool is_w = name == "sparse_linear.weight";
+    const int64_t want = is_w ? cfg_.hidden : 1;
+    SR_CHECK(numel == want, "encoder: weight '" + name + "' has " + std::to_string(numel) +
+                                " elements, expected " + std::to_string(want));
+    SR_CHECK(data != nullptr, "encoder: null weight data");
+    DeviceGuard g(device_);
+    begin(stream_);
+    SR_HIP(hipStreamSynchronize(stream_));
+    DevBuf& buf = is_w ? sparse_w_ : sparse_b_;
+    buf.reserve((size_t)want * sizeof(float));
+    SR_HIP(hipMemcpy(buf.p, data, (size_t)want * sizeof(float), hipMemcpyHostToDevice));
+    (is_w ? sparse_w_set_ : sparse_b_set_) = true;
+    return;
+  }
   auto it = targets_.find(name);
   SR_CHECK(it != targets_.end(), "encoder: unknown weight '" + name + "'");
   const Target& t = it->second;
@@ -320,8 +338,14 @@ void Encoder::ensure_ws(int64_t tokens, int B) {
 
 void Encoder::forward_dev(const int32_t* ids, const int32_t* mask, const int32_t* types, int B,
                           int S, int mode, int pool, void* out, int out_dtype, int ld_out,
-                          hipStream_t s) {
+                          hipStream_t s, const SparseOut* sparse) {
   SR_CHECK(B >= 0 && S >= 1, "encoder: bad batch shape");
+  if (sparse) {
+    SR_CHECK(mode == 0, "encoder: the sparse head belongs to the embedding forward");
+    sparse_terms_check_args(B, S, sparse->n_special);
+    SR_CHECK(sparse->n_special == 0 || sparse->special_ids, "encoder: null special_ids");
+    SR_CHECK(B == 0 || (sparse->terms && sparse->weights && sparse->count), "encoder: null sparse output");
+  }
   SR_CHECK(S <= cfg_.max_position - std::max(cfg_.position_offset, 0) - (cfg_.position_offset > 0 ? 1 : 0),
            "encoder: sequence longer than the position table");
   SR_CHECK(mode == 0 || cfg_.classifier == 1, "encoder: model has no classification head");
@@ -330,6 +354,9 @@ void Encoder::forward_dev(const int32_t* ids, const int32_t* mask, const int32_t
   SR_CHECK(mode == 1 || ld_out >= cfg_.hidden, "encoder: ld_out must be >= hidden");
   const std::string miss = missing();
   if (!miss.empty()) throw Error(SR_ERR_STATE, "encoder: weight not set: " + miss);
+  if (sparse && !(sparse_w_set_ && sparse_b_set_))
+    throw Error(SR_ERR_STATE, std::string("encoder: weight not set: sparse_linear.") +
+                                  (sparse_w_set_ ? "bias" : "weight"));
   if (B == 0) return;
   DeviceGuard g(device_);
   // s == nullptr is the HIP null stream (torch's default stream): use it as-is.
@@ -341,6 +368,12 @@ void Encoder::forward_dev(const int32_t* ids, const int32_t* mask, const int32_t
   if (mode == 1 && clst_.bytes < (size_t)std::min<int64_t>(B, seqs_per_chunk) * d * sizeof(float))
     SR_HIP(hipEventSynchronize(done_));
   if (mode == 1) clst_.reserve((size_t)std::min<int64_t>(B, seqs_per_chunk) * d * sizeof(float));
+  float* tok_weight = sparse ? sparse->tok_weight : nullptr;
+  if (sparse && !tok_weight) {
+    if (sparse_tw_.bytes < (size_t)B * S * sizeof(float)) SR_HIP(hipEventSynchronize(done_));
+    sparse_tw_.reserve((size_t)B * S * sizeof(float));
+    tok_weight = sparse_tw_.as<float>();
+  }
   half_t* h16 = h16_.as<half_t>();
   float* h32 = h32_.as<float>();
   half_t* qkv = qkv_.as<half_t>();
@@ -355,7 +388,8 @@ void Encoder::forward_dev(const int32_t* ids, const int32_t* mask, const int32_t
   // Only the first token's final state is consumed (CLS pooling / classification head): the last
   // layer runs attention for query row 0 only and its O-projection, LayerNorms and FFN on the
   // B CLS rows (exact: every other row of the last layer is dead).
-  const bool cls_only = (mode == 1) || (pool == SR_POOL_CLS);
+  // The sparse head reads every token's final state: its request keeps the full last layer.
+  const bool cls_only = !sparse && ((mode == 1) || (pool == SR_POOL_CLS));
 
   const bool fold = fold_enabled();
   if (fold) prepare_fold(s);
@@ -549,6 +583,13 @@ void Encoder::forward_dev(const int32_t* ids, const int32_t* mask, const int32_t
       const size_t esz = out_dtype == SR_DTYPE_F32 ? sizeof(float) : sizeof(half_t);
       launch_pool_l2(res16 ? (const void*)h16 : (const void*)h32, res16, cmask, nb, Sf, d, pool,
                      reinterpret_cast<char*>(out) + (size_t)b0 * ld_out * esz, out_dtype, ld_out, s);
+      if (sparse) {  // this chunk's token weights and terms, at the chunk's offset into B x S
+        float* tw = tok_weight + b0 * S;
+        launch_sparse_token_weights(res16 ? (const void*)h16 : (const void*)h32, res16, cmask,
+                                    sparse_w_.as<float>(), sparse_b_.as<float>(), M, d, tw, s);
+        launch_sparse_terms(cids, cmask, tw, nb, S, sparse->special_ids, sparse->n_special,
+                            sparse->terms + b0 * S, sparse->weights + b0 * S, sparse->count + b0, s);
+      }
     } else {
       float* t = clst_.as<float>();
       launch_gemm(EPI_BIAS_TANH_F32, h16, (int64_t)Sf * d, wc_.as<half_t>(), bc_.as<float>(),
@@ -579,6 +620,39 @@ void Encoder::forward_host(const int32_t* ids, const int32_t* mask, const int32_
   if (types) SR_HIP(hipMemcpyAsync(dtypes, types, n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
   forward_dev(dids, dmask, dtypes, B, S, mode, pool, dout, SR_DTYPE_F32, cfg_.hidden, stream_);
   SR_HIP(hipMemcpyAsync(out, dout, (size_t)out_elems * sizeof(float), hipMemcpyDeviceToHost, stream_));
+  SR_HIP(hipStreamSynchronize(stream_));
+}
+
+void Encoder::forward_sparse_host(const int32_t* ids, const int32_t* mask, const int32_t* types,
+                                  int B, int S, int pool, float* out_dense, const int32_t* special_ids,
+                                  int n_special, float* out_tok_weight, int32_t* out_terms,
+                                  float* out_weights, int32_t* out_count) {
+  SR_CHECK(B >= 0 && S >= 1, "encoder: bad batch shape");
+  SR_CHECK(B == 0 || (ids && mask && out_dense && out_terms && out_weights && out_count),
+           "encoder: null buffer");
+  sparse_terms_check_args(B, S, n_special);
+  if (B == 0) return;
+  DeviceGuard g(device_);
+  const size_t n = (size_t)B * S;
+  int32_t *dids, *dmask, *dtypes = nullptr, *dterms, *dcount;
+  float *dout, *dtw, *dw;
+  Carve c;
+  c.part(n, &dids, &dmask);
+  if (types) c.part(n, &dtypes);
+  c.part((size_t)B * cfg_.hidden, &dout);
+  c.part(n, &dtw, &dterms, &dw);
+  c.part((size_t)B, &dcount);
+  hostio_.carve(c);
+  SR_HIP(hipMemcpyAsync(dids, ids, n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+  SR_HIP(hipMemcpyAsync(dmask, mask, n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+  if (types) SR_HIP(hipMemcpyAsync(dtypes, types, n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+  const SparseOut so{special_ids, n_special, dtw, dterms, dw, dcount};
+  forward_dev(dids, dmask, dtypes, B, S, 0, pool, dout, SR_DTYPE_F32, cfg_.hidden, stream_, &so);
+  SR_HIP(hipMemcpyAsync(out_dense, dout, (size_t)B * cfg_.hidden * sizeof(float), hipMemcpyDeviceToHost, stream_));
+  if (out_tok_weight) SR_HIP(hipMemcpyAsync(out_tok_weight, dtw, n * sizeof(float), hipMemcpyDeviceToHost, stream_));
+  SR_HIP(hipMemcpyAsync(out_terms, dterms, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+  SR_HIP(hipMemcpyAsync(out_weights, dw, n * sizeof(float), hipMemcpyDeviceToHost, stream_));
+  SR_HIP(hipMemcpyAsync(out_count, dcount, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
   SR_HIP(hipStreamSynchronize(stream_));
 }
 

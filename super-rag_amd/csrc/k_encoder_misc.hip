@@ -892,3 +892,234 @@ void launch_vec_add(const float* a, const float* b, float* out, int n, hipStream
 }
 
 }  // namespace sr
+
+// ---- sparse head (learned-sparse retrieval; DESIGN.md "Learned-sparse retrieval") ------------------
+// bge-m3's sparse output: a weight per token, relu(sparse_linear(final state)), then one weight per
+// distinct token id of the sequence (the maximum over its positions).
+namespace sr {
+
+namespace {
+
+constexpr int STW_THREADS = 256;               // 4 waves, one token each
+constexpr int SPT_MAX_S = 8192;                // ids + weights of one sequence: 64 KiB of LDS
+constexpr int SPT_MAX_THREADS = 1024;
+constexpr int SPT_PER_THREAD = SPT_MAX_S / SPT_MAX_THREADS;
+
+// tw[t] = max(0, h[t] . w + bias) for mask[t] != 0, else 0.  A memory-bound GEMV over M x d: one wave
+// per token, 16-byte loads of the state, w staged once per workgroup in LDS, fp32 accumulation, a
+// wave reduction.
+template <bool F16>
+__global__ __launch_bounds__(STW_THREADS) void sparse_token_weights_kernel(
+    const void* __restrict__ h, const int32_t* __restrict__ mask, const float* __restrict__ w,
+    const float* __restrict__ bias, int M, int d, float* __restrict__ tw) {
+  __shared__ __attribute__((aligned(16))) float sw[2048];   // d <= 2048 (launcher)
+  const int tid = threadIdx.x, lane = tid & 63;
+  for (int i = tid; i < d; i += STW_THREADS) sw[i] = w[i];
+  __syncthreads();
+  const int t = blockIdx.x * (STW_THREADS / 64) + (tid >> 6);
+  if (t >= M) return;                                        // (wave-uniform)
+  if (mask[t] == 0) {
+    if (lane == 0) tw[t] = 0.f;
+    return;
+  }
+  float acc = 0.f;
+  if constexpr (F16) {
+    const half8* row = reinterpret_cast<const half8*>(reinterpret_cast<const half_t*>(h) + (int64_t)t * d);
+    for (int i = lane; i < (d >> 3); i += 64) {
+      const half8 x = row[i];
+      const float4v w0 = reinterpret_cast<const float4v*>(sw)[2 * i];
+      const float4v w1 = reinterpret_cast<const float4v*>(sw)[2 * i + 1];
+      acc += (float)x[0] * w0[0] + (float)x[1] * w0[1] + (float)x[2] * w0[2] + (float)x[3] * w0[3] +
+             (float)x[4] * w1[0] + (float)x[5] * w1[1] + (float)x[6] * w1[2] + (float)x[7] * w1[3];
+    }
+  } else {
+    const float4v* row = reinterpret_cast<const float4v*>(reinterpret_cast<const float*>(h) + (int64_t)t * d);
+    for (int i = lane; i < (d >> 2); i += 64) {
+      const float4v x = row[i];
+      const float4v w0 = reinterpret_cast<const float4v*>(sw)[i];
+      acc += x[0] * w0[0] + x[1] * w0[1] + x[2] * w0[2] + x[3] * w0[3];
+    }
+  }
+  acc = wave_sum(acc);
+  if (lane == 0) tw[t] = fmaxf(acc + bias[0], 0.f);
+}
+
+struct SparseSpecial {
+  int32_t id[16];
+  int n;
+};
+
+// exclusive prefix of v over the workgroup (waves of 64, then the wave totals); *total = the sum
+__device__ __forceinline__ int block_excl_scan(int v, int* s_wave, int* total) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nw = (blockDim.x + 63) >> 6;
+  int incl = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int u = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += u;
+  }
+  __syncthreads();   // s_wave may still be read from the previous scan
+  if (lane == 63) s_wave[wave] = incl;
+  __syncthreads();
+  int base = 0, tot = 0;
+  for (int i = 0; i < nw; ++i) {
+    const int c = s_wave[i];
+    if (i < wave) base += c;
+    tot += c;
+  }
+  *total = tot;
+  return base + incl - v;
+}
+
+// The exact token -> term collapse, one workgroup per sequence.  A position qualifies when mask != 0,
+// tw > 0 and its id is no special id.  (1) The qualifying (id, tw) pairs are compacted into LDS in
+// position order (a block scan).  (2) All pairs: every compacted entry i scans the nq ids (16-byte
+// broadcast LDS reads) for the maximum weight of its id and for an earlier entry of it.  (3) The
+// entries without an earlier one -- the first qualifying position of each distinct id -- are ranked
+// by a second block scan and written with that maximum; the slots past the count get -1 / 0.
+// Every thread owns a contiguous run of <= SPT_PER_THREAD positions / entries, so both scans keep
+// position order.  No atomics: the result does not depend on any execution order.
+__global__ __launch_bounds__(SPT_MAX_THREADS) void sparse_terms_kernel(
+    const int32_t* __restrict__ ids, const int32_t* __restrict__ mask, const float* __restrict__ tw,
+    int S, SparseSpecial sp, int32_t* __restrict__ out_terms, float* __restrict__ out_weights,
+    int32_t* __restrict__ out_count) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char sparse_smem[];
+  __shared__ int s_wave[SPT_MAX_THREADS / 64];
+  const int S4 = (S + 3) & ~3;
+  int32_t* sid = reinterpret_cast<int32_t*>(sparse_smem);   // [S4] compacted ids
+  float* swt = reinterpret_cast<float*>(sid + S4);          // [S4] their weights
+  const int b = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x;
+  const int64_t base = (int64_t)b * S;
+  // (1) compact
+  const int C = (S + nthr - 1) / nthr;                      // <= SPT_PER_THREAD (launcher)
+  const int p0 = tid * C;
+  int32_t my_id[SPT_PER_THREAD];
+  float my_w[SPT_PER_THREAD];
+  int nmine = 0;
+  unsigned ok_bits = 0u;
+#pragma unroll
+  for (int c = 0; c < SPT_PER_THREAD; ++c) {
+    const int p = p0 + c;
+    my_id[c] = 0;
+    my_w[c] = 0.f;
+    if (c < C && p < S) {
+      const int32_t id = ids[base + p];
+      const float x = tw[base + p];
+      bool ok = mask[base + p] != 0 && x > 0.f;
+      for (int j = 0; j < sp.n; ++j) ok = ok && id != sp.id[j];
+      if (ok) {
+        my_id[c] = id;
+        my_w[c] = x;
+        ok_bits |= 1u << c;
+        ++nmine;
+      }
+    }
+  }
+  int nq;
+  int q = block_excl_scan(nmine, s_wave, &nq);
+#pragma unroll
+  for (int c = 0; c < SPT_PER_THREAD; ++c)
+    if (ok_bits & (1u << c)) {
+      sid[q] = my_id[c];
+      swt[q] = my_w[c];
+      ++q;
+    }
+  __syncthreads();
+  // (2) all pairs over the nq compacted entries
+  const int C2 = (nq + nthr - 1) / nthr;
+  const int i0 = tid * C2;
+  float best[SPT_PER_THREAD];
+  int nfirst = 0;
+  unsigned first_bits = 0u;
+#pragma unroll
+  for (int c = 0; c < SPT_PER_THREAD; ++c) {
+    const int i = i0 + c;
+    best[c] = 0.f;
+    if (c < C2 && i < nq) {
+      const int32_t id = sid[i];
+      float m = swt[i];
+      bool first = true;
+      const int n4 = nq >> 2;
+      for (int j4 = 0; j4 < n4; ++j4) {
+        const int4 v = reinterpret_cast<const int4*>(sid)[j4];
+        const int j = j4 << 2;
+        if (v.x == id) { m = fmaxf(m, swt[j]); first = first && j >= i; }
+        if (v.y == id) { m = fmaxf(m, swt[j + 1]); first = first && j + 1 >= i; }
+        if (v.z == id) { m = fmaxf(m, swt[j + 2]); first = first && j + 2 >= i; }
+        if (v.w == id) { m = fmaxf(m, swt[j + 3]); first = first && j + 3 >= i; }
+      }
+      for (int j = n4 << 2; j < nq; ++j)
+        if (sid[j] == id) { m = fmaxf(m, swt[j]); first = first && j >= i; }
+      best[c] = m;
+      if (first) {
+        first_bits |= 1u << c;
+        ++nfirst;
+      }
+    }
+  }
+  // (3) rank the first occurrences and write
+  int cnt;
+  int r = block_excl_scan(nfirst, s_wave, &cnt);
+#pragma unroll
+  for (int c = 0; c < SPT_PER_THREAD; ++c)
+    if (first_bits & (1u << c)) {
+      out_terms[base + r] = sid[i0 + c];
+      out_weights[base + r] = best[c];
+      ++r;
+    }
+  for (int i = cnt + tid; i < S; i += nthr) {
+    out_terms[base + i] = -1;
+    out_weights[base + i] = 0.f;
+  }
+  if (tid == 0) out_count[b] = cnt;
+}
+
+}  // namespace
+
+void launch_sparse_token_weights(const void* h, bool h_f16, const int32_t* mask, const float* w,
+                                 const float* bias, int M, int d, float* tw, hipStream_t s) {
+  SR_CHECK(d % 8 == 0 && d <= 2048, "sparse head: hidden must be a multiple of 8, <= 2048");
+  if (M <= 0) return;
+  // the states, the mask and the output (w stays in cache)
+  ProfScope prof("sparse_token_weights", s, 2.0 * M * d, (double)M * (d * (h_f16 ? 2.0 : 4.0) + 8.0));
+  const dim3 grid((unsigned)ceil_div(M, STW_THREADS / 64));
+  if (h_f16)
+    hipLaunchKernelGGL(sparse_token_weights_kernel<true>, grid, dim3(STW_THREADS), 0, s, h, mask, w, bias,
+                       M, d, tw);
+  else
+    hipLaunchKernelGGL(sparse_token_weights_kernel<false>, grid, dim3(STW_THREADS), 0, s, h, mask, w, bias,
+                       M, d, tw);
+  SR_LAUNCH_CHECK();
+}
+
+void sparse_terms_check_args(int B, int S, int n_special) {
+  SR_CHECK(B >= 0, "sparse_terms: negative batch");
+  SR_CHECK(S >= 1 && S <= SPT_MAX_S, "sparse_terms: S must be in [1, 8192]");
+  SR_CHECK(n_special >= 0 && n_special <= 16, "sparse_terms: n_special must be in [0, 16]");
+}
+
+void launch_sparse_terms(const int32_t* ids, const int32_t* mask, const float* tw, int B, int S,
+                         const int32_t* special_ids, int n_special, int32_t* out_terms,
+                         float* out_weights, int32_t* out_count, hipStream_t s) {
+  sparse_terms_check_args(B, S, n_special);
+  SR_CHECK(n_special == 0 || special_ids, "sparse_terms: null special_ids");
+  if (B == 0) return;
+  SparseSpecial sp;
+  sp.n = n_special;
+  for (int i = 0; i < 16; ++i) sp.id[i] = i < n_special ? special_ids[i] : 0;
+  const int threads = (int)std::min<int64_t>(SPT_MAX_THREADS, round_up(S, 64));
+  const size_t smem = (size_t)round_up(S, 4) * 8;
+  static bool attr_set = false;
+  if (!attr_set) {
+    SR_HIP(hipFuncSetAttribute((const void*)sparse_terms_kernel,
+                               hipFuncAttributeMaxDynamicSharedMemorySize, SPT_MAX_S * 8));
+    attr_set = true;
+  }
+  // ids, mask and weights in, terms and weights out, the count
+  ProfScope prof("sparse_terms", s, 0.0, (double)B * (S * 20.0 + 4.0));
+  hipLaunchKernelGGL(sparse_terms_kernel, dim3(B), dim3(threads), smem, s, ids, mask, tw, S, sp, out_terms,
+                     out_weights, out_count);
+  SR_LAUNCH_CHECK();
+}
+
+}  // namespace sr

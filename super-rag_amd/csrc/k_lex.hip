@@ -32,6 +32,11 @@
 //   R1 lex_score_rows: one wave per pair walks the row's own forward postings through foff and sums
 //      the same fixed-point weights for the postings whose term is one of the query's scored terms
 //      (term table in LDS, binary search): the exact score the search gives that row.
+// Impact mode (learned-sparse retrieval; LexIndex created with SR_LEX_IMPACT):
+//   the low 32 bits of fval / post hold the fp32 bits of a document weight in (0, 16] where BM25
+//   holds tf; nothing else about the layout changes, so the rebuild, L0 and L2 run as they are.  L1
+//   and R1 have an IMPACT variant: LexTerm::idf carries the query weight, a posting adds
+//   max(1, rint(fl32(qw * dw) * 2^16)) (one rounded multiply) and no document length is read.
 // Fusion:
 //   F1 rrf_fuse: one workgroup per query: rrf score of a row = sum over the lists of
 //      1 / (rank + rank_const) in fp64 (list a first, as graphiti accumulates), ordered by score
@@ -107,6 +112,14 @@ __device__ __forceinline__ uint32_t bm25_fixed(float idf, float tf, float dl, fl
   return q < 1.f ? 1u : (uint32_t)q;
 }
 
+// impact mode: the posting's weight times the query's, one rounded fp32 multiply, in the same 2^-16
+// fixed point (the host bounds qw so that p * 2^16 < 2^32 - 1: LexIndex::weighted_query_terms)
+__device__ __forceinline__ uint32_t impact_fixed(float qw, float dw) {
+  const float p = qw * dw;
+  const float q = rintf(p * LEX_SCALE);
+  return q < 1.f ? 1u : (uint32_t)q;
+}
+
 // bnd[t][blk] = first posting of term slot t whose row is >= blk * LEX_RB (postings are sorted by
 // row inside a term, and a posting's u64 orders by row first), blk in [0, NB]
 __global__ void lex_bounds_kernel(const LexTerm* __restrict__ terms, int nslots, int NB,
@@ -129,6 +142,9 @@ __global__ void lex_bounds_kernel(const LexTerm* __restrict__ terms, int nslots,
 // accumulated with LDS atomics into a 8192-row fixed-point accumulator, then every non-zero
 // entry is appended to the query's candidate keys (score << 32 | ~row), one counter atomic per
 // wave.  Postings of a block are contiguous in each term's list: streaming 8-byte loads.
+// IMPACT: the posting's low half is an fp32 weight and LexTerm::idf the query's (mult 1); dlen,
+// avgdl, k1 and b are not read.
+template <bool IMPACT>
 __global__ __launch_bounds__(LEX_THREADS) void lex_score_kernel(
     const LexTerm* __restrict__ terms, const int* __restrict__ slot_off, const int32_t* __restrict__ bnd,
     int NB, const uint64_t* __restrict__ post, const int32_t* __restrict__ dlen,
@@ -154,7 +170,7 @@ __global__ __launch_bounds__(LEX_THREADS) void lex_score_kernel(
   __syncthreads();
   if (s_total == 0) return;  // uniform: no posting of this query in this row block
   for (int i = tid; i < LEX_RB; i += LEX_THREADS) acc[i] = 0u;
-  const float avgdl = *avgdl_p;  // (host path: uploaded; device path: lex_qprep_kernel)
+  const float avgdl = IMPACT ? 1.f : *avgdl_p;  // (host path: uploaded; device path: lex_qprep_kernel)
   const float one_minus_b = 1.f - b, k1p1 = k1 + 1.f;
   const int64_t r0 = (int64_t)blk * LEX_RB;
   for (int tb = s0; tb < s1; tb += TB) {
@@ -185,9 +201,14 @@ __global__ __launch_bounds__(LEX_THREADS) void lex_score_kernel(
       const uint64_t v = post[e.start + s_lo[lo_t] + (p - s_pre[lo_t])];
       const uint32_t row = (uint32_t)(v >> 32);
       if (elig && !elig[row]) continue;
-      const float tf = (float)(uint32_t)v;
-      const float dl = (float)dlen[row];
-      const uint32_t sc = bm25_fixed(e.idf, tf, dl, avgdl, k1, b, one_minus_b, k1p1) * (uint32_t)e.mult;
+      uint32_t sc;
+      if constexpr (IMPACT) {
+        sc = impact_fixed(e.idf, __uint_as_float((uint32_t)v));
+      } else {
+        const float tf = (float)(uint32_t)v;
+        const float dl = (float)dlen[row];
+        sc = bm25_fixed(e.idf, tf, dl, avgdl, k1, b, one_minus_b, k1p1) * (uint32_t)e.mult;
+      }
       atomicAdd(&acc[row - r0], sc);
     }
   }
@@ -245,6 +266,8 @@ __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
   return v;
 }
 
+// IMPACT: qt_idf holds the query weights and the posting's low half an fp32 weight (multiplicity 1).
+template <bool IMPACT>
 __global__ __launch_bounds__(LSR_THREADS) void lex_score_rows_kernel(
     const int32_t* __restrict__ fterm, const uint64_t* __restrict__ fval,
     const int64_t* __restrict__ foff, int64_t P, const int32_t* __restrict__ dlen,
@@ -271,7 +294,7 @@ __global__ __launch_bounds__(LSR_THREADS) void lex_score_rows_kernel(
         p0 = foff[r];
         p1 = foff[r + 1];
         p1 = p1 < P ? p1 : P;
-        dl = (float)dlen[r];
+        if constexpr (!IMPACT) dl = (float)dlen[r];
       }
     }
     uint32_t acc = 0u;
@@ -294,8 +317,12 @@ __global__ __launch_bounds__(LSR_THREADS) void lex_score_rows_kernel(
           else hi = mid;
         }
         if (lo < nt && s_term[lo] == t) {
-          const float tf = (float)(uint32_t)fval[p];
-          acc += bm25_fixed(s_idf[lo], tf, dl, avgdl, k1, b, one_minus_b, k1p1) * (uint32_t)s_mult[lo];
+          if constexpr (IMPACT) {
+            acc += impact_fixed(s_idf[lo], __uint_as_float((uint32_t)fval[p]));
+          } else {
+            const float tf = (float)(uint32_t)fval[p];
+            acc += bm25_fixed(s_idf[lo], tf, dl, avgdl, k1, b, one_minus_b, k1p1) * (uint32_t)s_mult[lo];
+          }
         }
       }
     }
@@ -602,8 +629,10 @@ void launch_rrf_fuse(const int64_t* rows_a, int ka, const int64_t* rows_b, int k
 
 // ================================================================================================
 // LexIndex
-LexIndex::LexIndex(int device, float k1, float b) : device_(device), k1_(k1), b_(b) {
+LexIndex::LexIndex(int device, float k1, float b, int mode)
+    : device_(device), k1_(k1), b_(b), mode_(mode) {
   SR_CHECK(k1 >= 0.f && b >= 0.f && b <= 1.f, "lex: need k1 >= 0 and 0 <= b <= 1");
+  SR_CHECK(mode == SR_LEX_BM25 || mode == SR_LEX_IMPACT, "lex: unknown scoring mode");
   DeviceGuard g(device_);
   SR_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
   SR_HIP(hipEventCreateWithFlags(&done_, hipEventDisableTiming));
@@ -647,9 +676,44 @@ void LexIndex::add(const int64_t* off, const int32_t* terms, const int32_t* tf, 
       SR_CHECK(terms[p] >= 0 && terms[p] < kLexMaxVocab, "lex.add: term id out of range [0, 2^26)");
       SR_CHECK(tf[p] >= 1, "lex.add: term frequency must be >= 1");
       val[(size_t)p] = ((uint64_t)(rows_ + i) << 32) | (uint32_t)tf[p];
-      vocab_ = std::max<int64_t>(vocab_, (int64_t)terms[p] + 1);
     }
   }
+  append(off, terms, val.data(), dl, n);
+}
+
+void LexIndex::add_weighted(const int64_t* off, const int32_t* terms, const float* weights, int64_t n,
+                            int64_t* first_row) {
+  SR_CHECK(n >= 0, "lex.add_weighted: negative count");
+  if (first_row) *first_row = rows_;
+  if (n == 0) return;
+  SR_CHECK(off && off[0] == 0, "lex.add_weighted: off[0] must be 0");
+  for (int64_t i = 0; i < n; ++i)
+    SR_CHECK(off[i + 1] >= off[i], "lex.add_weighted: off must be non-decreasing");
+  const int64_t P = off[n];
+  SR_CHECK(P == 0 || (terms && weights), "lex.add_weighted: null term arrays");
+  SR_CHECK(rows_ + n <= (int64_t)0x7fffffff, "lex.add: more than 2^31 rows");
+  std::vector<uint64_t> val((size_t)P);
+  std::vector<int32_t> dl((size_t)n);   // the snapshot's length slot: the row's postings
+  for (int64_t i = 0; i < n; ++i) {
+    SR_CHECK(off[i + 1] - off[i] <= (int64_t)0x7fffffff, "lex.add_weighted: more than 2^31 terms in a row");
+    dl[(size_t)i] = (int32_t)(off[i + 1] - off[i]);
+    for (int64_t p = off[i]; p < off[i + 1]; ++p) {
+      SR_CHECK(terms[p] >= 0 && terms[p] < kLexMaxVocab, "lex.add_weighted: term id out of range [0, 2^26)");
+      const float w = weights[p];
+      SR_CHECK(std::isfinite(w) && w > 0.f && w <= SR_IMPACT_MAX_WEIGHT,
+               "lex.add_weighted: document weights must be finite and in (0, 16]");
+      uint32_t bits;
+      std::memcpy(&bits, &w, 4);
+      val[(size_t)p] = ((uint64_t)(rows_ + i) << 32) | bits;
+    }
+  }
+  append(off, terms, val.data(), dl.data(), n);
+}
+
+void LexIndex::append(const int64_t* off, const int32_t* terms, const uint64_t* val, const int32_t* dl,
+                      int64_t n) {
+  const int64_t P = off[n];
+  for (int64_t p = 0; p < P; ++p) vocab_ = std::max<int64_t>(vocab_, (int64_t)terms[p] + 1);
   DeviceGuard g(device_);
   begin(stream_);
   grow_copy(fterm_, (size_t)P_ * 4, (size_t)(P_ + P) * 4, stream_);
@@ -663,7 +727,7 @@ void LexIndex::add(const int64_t* off, const int32_t* terms, const int32_t* tf, 
   SR_HIP(hipMemcpyAsync(foff_.as<int64_t>() + rows_, fo.data(), fo.size() * 8, hipMemcpyHostToDevice, stream_));
   if (P) {
     SR_HIP(hipMemcpyAsync(fterm_.as<int32_t>() + P_, terms, (size_t)P * 4, hipMemcpyHostToDevice, stream_));
-    SR_HIP(hipMemcpyAsync(fval_.as<uint64_t>() + P_, val.data(), (size_t)P * 8, hipMemcpyHostToDevice, stream_));
+    SR_HIP(hipMemcpyAsync(fval_.as<uint64_t>() + P_, val, (size_t)P * 8, hipMemcpyHostToDevice, stream_));
   }
   SR_HIP(hipMemcpyAsync(dlen_.as<int32_t>() + rows_, dl, (size_t)n * 4, hipMemcpyHostToDevice, stream_));
   SR_HIP(hipMemsetAsync(live_.as<uint8_t>() + rows_, 1, (size_t)n, stream_));
@@ -798,9 +862,7 @@ void LexIndex::df(const int32_t* terms, int n, int64_t* out) {
 // ---- host-side query preparation shared by search_dev and score_rows_dev -------------------------
 namespace {
 
-struct LexQT {
-  int32_t term, mult;
-};
+using LexQT = LexIndex::QTerm;
 
 // The terms of one query that are scored: distinct ids in [0, vocab) with live df > 0, in
 // first-occurrence order, mult = occurrences in the query.
@@ -816,7 +878,7 @@ std::vector<LexQT> lex_query_terms(const int32_t* qterms, int64_t p0, int64_t p1
         ++e.mult;
         seen = true;
       }
-    if (!seen) v.push_back({t, 1});
+    if (!seen) v.push_back({t, 1, 0.f});
   }
   return v;
 }
@@ -881,29 +943,45 @@ void LexIndex::search_dev(const int64_t* qoff, const int32_t* qterms, int B, int
   begin(s);
   rebuild(s);
   const uint8_t* elig = eligibility(allow, mask_key, s);
-  // per query: distinct known terms with multiplicity, and the touched-list capacity
+  // per query: distinct known terms with multiplicity
   std::vector<std::vector<LexQT>> qt((size_t)B);
-  std::vector<int64_t> cap((size_t)B, 0);
   for (int b = 0; b < B; ++b) {
     SR_CHECK(qoff[b + 1] >= qoff[b], "lex.search: qoff must be non-decreasing");
     qt[(size_t)b] = lex_query_terms(qterms, qoff[b], qoff[b + 1], vocab_, df_host_);
-    for (const LexQT& e : qt[(size_t)b]) cap[(size_t)b] += df_host_[(size_t)e.term];
-    cap[(size_t)b] = std::min<int64_t>(cap[(size_t)b], rows_);
   }
   // statistics: this index's live rows, or the caller's corpus-wide ones (row-sharded corpus:
   // every shard then scores with the same N, avgdl and df, so merged results equal one index's)
   const LexStatsHost stats(glob, live_n_, sum_dl_);
-  const int64_t N_live = stats.n_live, sum_dl = stats.sum_dl;
-  auto term_df = [&](int32_t t) -> int64_t { return stats.df(t, df_host_); };
+  for (auto& v : qt)
+    for (LexQT& e : v) e.w = idf(stats.df(e.term, df_host_), stats.n_live);
+  search_terms(qt, k, elig, avgdl(stats.sum_dl, stats.n_live), out_score, out_rows, s, row_offset,
+               out_fixed);
+  end(s);
+}
+
+// The scoring launches of a prepared batch (qt[b]: query b's scored terms, w = idf or, in impact
+// mode, the query weight): query blocks, L0 bounds, L1 score, L2 select.
+void LexIndex::search_terms(const std::vector<std::vector<QTerm>>& qt, int k, const uint8_t* elig,
+                            float adl, float* out_score, int64_t* out_rows, hipStream_t s,
+                            int64_t row_offset, uint32_t* out_fixed) {
+  const int B = (int)qt.size();
+  const bool impact = mode_ == SR_LEX_IMPACT;
+  // the touched-list capacity of every query
+  std::vector<int64_t> cap((size_t)B, 0);
+  for (int b = 0; b < B; ++b) {
+    for (const LexQT& e : qt[(size_t)b]) cap[(size_t)b] += df_host_[(size_t)e.term];
+    cap[(size_t)b] = std::min<int64_t>(cap[(size_t)b], rows_);
+  }
   // query blocks: candidate keys within LEX_KEY_BUDGET; grid (queries, row blocks), so the
   // workgroups in flight belong to many queries
   const int64_t rows = std::max<int64_t>(rows_, 1);
   const int NB = (int)ceil_div(rows, LEX_RB);
   SR_CHECK(NB <= 65535, "lex.search: more than 2^30 rows per index");
-  const float adl = avgdl(sum_dl, N_live);
   static bool attr_set = false;
   if (!attr_set) {
-    SR_HIP(hipFuncSetAttribute((const void*)lex_score_kernel,
+    SR_HIP(hipFuncSetAttribute((const void*)lex_score_kernel<false>,
+                               hipFuncAttributeMaxDynamicSharedMemorySize, LEX_RB * 4));
+    SR_HIP(hipFuncSetAttribute((const void*)lex_score_kernel<true>,
                                hipFuncAttributeMaxDynamicSharedMemorySize, LEX_RB * 4));
     SR_HIP(hipFuncSetAttribute((const void*)lex_select_kernel,
                                hipFuncAttributeMaxDynamicSharedMemorySize, sizeof(LexSelSmem)));
@@ -922,7 +1000,7 @@ void LexIndex::search_dev(const int64_t* qoff, const int32_t* qterms, int B, int
       koff[(size_t)i + 1] = koff[(size_t)i] + cap[(size_t)(b0 + i)];
       for (const LexQT& e : qt[(size_t)(b0 + i)]) {
         const int64_t len = df_host_[(size_t)e.term];
-        slots.push_back({off_host_[(size_t)e.term], (int32_t)len, idf(term_df(e.term), N_live), e.mult, 0});
+        slots.push_back({off_host_[(size_t)e.term], (int32_t)len, e.w, e.mult, 0});
         scored += len;
       }
       slot_off[(size_t)i + 1] = (int)slots.size();
@@ -943,11 +1021,20 @@ void LexIndex::search_dev(const int64_t* qoff, const int32_t* qterms, int B, int
       hipLaunchKernelGGL(lex_bounds_kernel, dim3((unsigned)ceil_div(nb, 256)), dim3(256), 0, s, d_sl,
                          nslots, NB, post_.as<uint64_t>(), d_bnd);
       SR_LAUNCH_CHECK();
-      ProfScope prof("lex_score", s, 0.0, (double)scored * 12.0);
-      hipLaunchKernelGGL(lex_score_kernel, dim3((unsigned)qb, (unsigned)NB), dim3(LEX_THREADS),
-                         LEX_RB * 4, s, d_sl, d_so, d_bnd, NB, post_.as<uint64_t>(),
-                         dlen_.as<int32_t>(), elig, rows_, d_avg, k1_, b_, d_cnt, d_ko, d_keys);
-      SR_LAUNCH_CHECK();
+      if (impact) {
+        // a posting (8 B) and its accumulator update: no per-row length is read
+        ProfScope prof("lex_score_impact", s, 0.0, (double)scored * 8.0);
+        hipLaunchKernelGGL(lex_score_kernel<true>, dim3((unsigned)qb, (unsigned)NB), dim3(LEX_THREADS),
+                           LEX_RB * 4, s, d_sl, d_so, d_bnd, NB, post_.as<uint64_t>(),
+                           dlen_.as<int32_t>(), elig, rows_, d_avg, k1_, b_, d_cnt, d_ko, d_keys);
+        SR_LAUNCH_CHECK();
+      } else {
+        ProfScope prof("lex_score", s, 0.0, (double)scored * 12.0);
+        hipLaunchKernelGGL(lex_score_kernel<false>, dim3((unsigned)qb, (unsigned)NB), dim3(LEX_THREADS),
+                           LEX_RB * 4, s, d_sl, d_so, d_bnd, NB, post_.as<uint64_t>(),
+                           dlen_.as<int32_t>(), elig, rows_, d_avg, k1_, b_, d_cnt, d_ko, d_keys);
+        SR_LAUNCH_CHECK();
+      }
     }
     {
       ProfScope prof("lex_select", s, 0.0, (double)koff[(size_t)qb] * 8.0);
@@ -961,7 +1048,71 @@ void LexIndex::search_dev(const int64_t* qoff, const int32_t* qterms, int B, int
     SR_HIP(hipStreamSynchronize(s));
     b0 += qb;
   }
-  end(s);
+}
+
+// Impact-mode query preparation, host only (no device work, no index state but the vocabulary
+// mirror used afterwards): weights finite and >= 0; per query the distinct ids with a weight > 0,
+// a repeated id keeping its maximum, in first-occurrence order; the overflow bound over them.
+std::vector<std::vector<LexIndex::QTerm>> LexIndex::weighted_query_terms(
+    const int64_t* qoff, const int32_t* qterms, const float* qweights, int B) const {
+  std::vector<std::vector<QTerm>> qt((size_t)B);
+  for (int b = 0; b < B; ++b) {
+    SR_CHECK(qoff[b + 1] >= qoff[b], "lex.search_weighted: qoff must be non-decreasing");
+    std::vector<QTerm>& v = qt[(size_t)b];
+    for (int64_t p = qoff[b]; p < qoff[b + 1]; ++p) {
+      const float w = qweights[p];
+      SR_CHECK(std::isfinite(w) && w >= 0.f, "lex.search_weighted: query weights must be finite and >= 0");
+      if (w == 0.f) continue;
+      bool seen = false;
+      for (QTerm& e : v)
+        if (e.term == qterms[p]) {
+          e.w = std::max(e.w, w);
+          seen = true;
+        }
+      if (!seen) v.push_back({qterms[p], 1, w});
+    }
+    // every posting adds at most rint(16 qw 2^16) or the clamp's 1: the sum over the query's
+    // terms bounds a row's uint32 accumulator
+    double bound = 0.0;
+    for (const QTerm& e : v) bound += (double)SR_IMPACT_MAX_WEIGHT * (double)e.w * 65536.0 + 1.0;
+    SR_CHECK(bound < 4294967296.0, "lex.search_weighted: query weights too large (sum of 16 * w * 2^16 + 1 "
+                                   "over the query's terms must stay below 2^32)");
+  }
+  return qt;
+}
+
+void LexIndex::search_weighted_host(const int64_t* qoff, const int32_t* qterms, const float* qweights,
+                                    int B, int k, const uint8_t* allow, int64_t mask_key,
+                                    float* out_score, int64_t* out_rows, uint32_t* out_fixed) {
+  SR_CHECK(B >= 0, "lex.search_weighted: negative batch");
+  SR_CHECK(k >= 1 && k <= SR_MAX_TOPK, "lex.search: top_k must be in [1, 1024]");
+  if (B == 0) return;
+  SR_CHECK(out_score && out_rows, "lex.search: null output");
+  SR_CHECK(qoff && qoff[0] == 0, "lex.search_weighted: qoff[0] must be 0");
+  std::vector<std::vector<QTerm>> qt = weighted_query_terms(qoff, qterms, qweights, B);
+  DeviceGuard g(device_);
+  const size_t ob = (size_t)B * k;
+  float* ds;
+  int64_t* dr;
+  uint32_t* dfx = nullptr;
+  Carve c;
+  c.part(ob, &ds, &dr);
+  if (out_fixed) c.part(ob, &dfx);
+  out_.carve(c);
+  begin(stream_);
+  rebuild(stream_);
+  const uint8_t* elig = eligibility(allow, mask_key, stream_);
+  // only now is it known which ids the index scores (live postings)
+  for (auto& v : qt)
+    v.erase(std::remove_if(v.begin(), v.end(), [&](const QTerm& e) {
+              return e.term < 0 || e.term >= vocab_ || df_host_[(size_t)e.term] == 0;
+            }), v.end());
+  search_terms(qt, k, elig, 1.f, ds, dr, stream_, 0, dfx);
+  end(stream_);
+  SR_HIP(hipMemcpyAsync(out_score, ds, ob * 4, hipMemcpyDeviceToHost, stream_));
+  SR_HIP(hipMemcpyAsync(out_rows, dr, ob * 8, hipMemcpyDeviceToHost, stream_));
+  if (out_fixed) SR_HIP(hipMemcpyAsync(out_fixed, dfx, ob * 4, hipMemcpyDeviceToHost, stream_));
+  SR_HIP(hipStreamSynchronize(stream_));
 }
 
 void LexIndex::query_stats_dev(const int32_t* tok, const int32_t* qlen, int B, int Lq,
@@ -993,7 +1144,7 @@ void LexIndex::search_tok_dev(const int32_t* tok, const int32_t* qlen, int B, in
   SR_CHECK(NB <= 65535, "lex.search: more than 2^30 rows per index");
   static bool attr_set = false;
   if (!attr_set) {
-    SR_HIP(hipFuncSetAttribute((const void*)lex_score_kernel,
+    SR_HIP(hipFuncSetAttribute((const void*)lex_score_kernel<false>,
                                hipFuncAttributeMaxDynamicSharedMemorySize, LEX_RB * 4));
     SR_HIP(hipFuncSetAttribute((const void*)lex_select_kernel,
                                hipFuncAttributeMaxDynamicSharedMemorySize, sizeof(LexSelSmem)));
@@ -1048,7 +1199,7 @@ void LexIndex::search_tok_dev(const int32_t* tok, const int32_t* qlen, int B, in
                          (int)ns, NB, post_.as<uint64_t>(), d_bnd);
       SR_LAUNCH_CHECK();
       ProfScope prof("lex_score", s, 0.0, 0.0);
-      hipLaunchKernelGGL(lex_score_kernel, dim3((unsigned)qb, (unsigned)NB), dim3(LEX_THREADS),
+      hipLaunchKernelGGL(lex_score_kernel<false>, dim3((unsigned)qb, (unsigned)NB), dim3(LEX_THREADS),
                          LEX_RB * 4, s, d_sl, d_so, d_bnd, NB, post_.as<uint64_t>(),
                          dlen_.as<int32_t>(), (const uint8_t*)nullptr, rows_, d_avg, k1_, b_, d_cnt,
                          d_ko, d_keys);
@@ -1101,16 +1252,32 @@ void LexIndex::score_rows_dev(const int64_t* qoff, const int32_t* qterms, int B,
   begin(s);
   rebuild(s);   // df_host_ (which terms are scored, and the idf) comes from the inverted index
   const LexStatsHost stats(glob, live_n_, sum_dl_);
+  std::vector<std::vector<LexQT>> qt((size_t)B);
+  for (int b = 0; b < B; ++b) {
+    std::vector<LexQT>& v = qt[(size_t)b];
+    v = lex_query_terms(qterms, qoff[b], qoff[b + 1], vocab_, df_host_);
+    std::sort(v.begin(), v.end(), [](const LexQT& x, const LexQT& y) { return x.term < y.term; });
+    for (LexQT& e : v) e.w = idf(stats.df(e.term, df_host_), stats.n_live);
+  }
+  score_rows_terms(qt, rows, K, row_offset, avgdl(stats.sum_dl, stats.n_live), miss, out_score,
+                   out_fixed, s);
+  end(s);
+}
+
+// The launch of a prepared batch of (query, row) pairs (qt[b]: query b's scored terms ascending by
+// id, w = idf or, in impact mode, the query weight).
+void LexIndex::score_rows_terms(const std::vector<std::vector<QTerm>>& qt, const int64_t* rows, int K,
+                                int64_t row_offset, float adl, float miss, float* out_score,
+                                uint32_t* out_fixed, hipStream_t s) {
+  const int B = (int)qt.size();
   std::vector<int> qt_off((size_t)B + 1, 0);
   std::vector<int32_t> term, mult;
   std::vector<float> idfv;
   for (int b = 0; b < B; ++b) {
-    std::vector<LexQT> v = lex_query_terms(qterms, qoff[b], qoff[b + 1], vocab_, df_host_);
-    std::sort(v.begin(), v.end(), [](const LexQT& x, const LexQT& y) { return x.term < y.term; });
-    for (const LexQT& e : v) {
+    for (const LexQT& e : qt[(size_t)b]) {
       term.push_back(e.term);
       mult.push_back(e.mult);
-      idfv.push_back(idf(stats.df(e.term, df_host_), stats.n_live));
+      idfv.push_back(e.w);
     }
     SR_CHECK(term.size() <= (size_t)0x7fffffff, "lex.score_rows: more than 2^31 query terms");
     qt_off[(size_t)b + 1] = (int)term.size();
@@ -1132,18 +1299,27 @@ void LexIndex::score_rows_dev(const int64_t* qoff, const int32_t* qterms, int B,
   {
     // expected traffic at the index's mean postings per row (the host keeps no per-row counts):
     // row id, two offsets, length, live flag and the two outputs per pair, 12 B per posting
+    // (impact mode reads no length)
     const double per_row = rows_ > 0 ? (double)P_ / (double)rows_ : 0.0;
-    ProfScope prof("lex_score_rows", s, 0.0, (double)B * K * (37.0 + per_row * 12.0));
-    hipLaunchKernelGGL(lex_score_rows_kernel, dim3((unsigned)ceil_div(K, LSR_PAIRS), (unsigned)std::min(B, 65535)),
-                       dim3(LSR_THREADS), 0, s, fterm_.as<int32_t>(), fval_.as<uint64_t>(),
-                       foff_.as<int64_t>(), P_, dlen_.as<int32_t>(), live_.as<uint8_t>(), rows_, d_off,
-                       d_t, d_i, d_m, rows, B, K, row_offset, avgdl(stats.sum_dl, stats.n_live), k1_, b_,
-                       miss, out_score, out_fixed);
-    SR_LAUNCH_CHECK();
+    const dim3 grid((unsigned)ceil_div(K, LSR_PAIRS), (unsigned)std::min(B, 65535));
+    if (mode_ == SR_LEX_IMPACT) {
+      ProfScope prof("lex_score_rows_impact", s, 0.0, (double)B * K * (33.0 + per_row * 12.0));
+      hipLaunchKernelGGL(lex_score_rows_kernel<true>, grid, dim3(LSR_THREADS), 0, s,
+                         fterm_.as<int32_t>(), fval_.as<uint64_t>(), foff_.as<int64_t>(), P_,
+                         dlen_.as<int32_t>(), live_.as<uint8_t>(), rows_, d_off, d_t, d_i, d_m, rows, B,
+                         K, row_offset, adl, k1_, b_, miss, out_score, out_fixed);
+      SR_LAUNCH_CHECK();
+    } else {
+      ProfScope prof("lex_score_rows", s, 0.0, (double)B * K * (37.0 + per_row * 12.0));
+      hipLaunchKernelGGL(lex_score_rows_kernel<false>, grid, dim3(LSR_THREADS), 0, s,
+                         fterm_.as<int32_t>(), fval_.as<uint64_t>(), foff_.as<int64_t>(), P_,
+                         dlen_.as<int32_t>(), live_.as<uint8_t>(), rows_, d_off, d_t, d_i, d_m, rows, B,
+                         K, row_offset, adl, k1_, b_, miss, out_score, out_fixed);
+      SR_LAUNCH_CHECK();
+    }
   }
   // the host vectors above back async copies: finish before they go away
   SR_HIP(hipStreamSynchronize(s));
-  end(s);
 }
 
 void LexIndex::score_rows_host(const int64_t* qoff, const int32_t* qterms, int B, const int64_t* rows,
@@ -1168,13 +1344,45 @@ void LexIndex::score_rows_host(const int64_t* qoff, const int32_t* qterms, int B
   SR_HIP(hipStreamSynchronize(stream_));
 }
 
+void LexIndex::score_rows_weighted_host(const int64_t* qoff, const int32_t* qterms,
+                                        const float* qweights, int B, const int64_t* rows, int K,
+                                        float* out_score, uint32_t* out_fixed) {
+  SR_CHECK(B >= 0 && K >= 0, "lex.score_rows: negative shape");
+  if (B == 0 || K == 0) return;
+  SR_CHECK(qoff && rows && out_score, "lex.score_rows: null buffer");
+  SR_CHECK(qoff[0] == 0, "lex.score_rows: qoff[0] must be 0");
+  std::vector<std::vector<QTerm>> qt = weighted_query_terms(qoff, qterms, qweights, B);
+  DeviceGuard g(device_);
+  const size_t n = (size_t)B * K;
+  int64_t* dr;
+  float* ds;
+  uint32_t* dfx;
+  Carve c;
+  c.part(n, &dr, &ds, &dfx);
+  out_.carve(c);
+  begin(stream_);
+  SR_HIP(hipMemcpyAsync(dr, rows, n * 8, hipMemcpyHostToDevice, stream_));
+  rebuild(stream_);   // df_host_: which terms the search scores
+  for (auto& v : qt) {
+    v.erase(std::remove_if(v.begin(), v.end(), [&](const QTerm& e) {
+              return e.term < 0 || e.term >= vocab_ || df_host_[(size_t)e.term] == 0;
+            }), v.end());
+    std::sort(v.begin(), v.end(), [](const QTerm& x, const QTerm& y) { return x.term < y.term; });
+  }
+  score_rows_terms(qt, dr, K, 0, 1.f, 0.f, ds, out_fixed ? dfx : nullptr, stream_);
+  end(stream_);
+  SR_HIP(hipMemcpyAsync(out_score, ds, n * 4, hipMemcpyDeviceToHost, stream_));
+  if (out_fixed) SR_HIP(hipMemcpyAsync(out_fixed, dfx, n * 4, hipMemcpyDeviceToHost, stream_));
+  SR_HIP(hipStreamSynchronize(stream_));
+}
+
 void LexIndex::stats(int64_t* rows, int64_t* live, int64_t* postings, int64_t* vocab,
                      double* avgdl_out) {
   if (rows) *rows = rows_;
   if (live) *live = live_n_;
   if (postings) *postings = P_;
   if (vocab) *vocab = vocab_;
-  if (avgdl_out) *avgdl_out = live_n_ > 0 ? (double)sum_dl_ / (double)live_n_ : 0.0;
+  if (avgdl_out) *avgdl_out = (mode_ == SR_LEX_BM25 && live_n_ > 0) ? (double)sum_dl_ / (double)live_n_ : 0.0;
 }
 
 // Download the forward index (row order) to the host.
@@ -1189,7 +1397,9 @@ void LexIndex::forward(std::vector<int32_t>& fterm, std::vector<uint64_t>& fval)
 }
 
 // Snapshot (little endian): "SRMILEX1", float k1, float b, int64 rows, int64 P,
-// rows x int32 dl, rows x u8 live, P x int32 term, P x u64 (row << 32 | tf).
+// rows x int32 dl, rows x u8 live, P x int32 term, P x u64 (row << 32 | tf).  An impact index
+// writes "SRMILEX2" and the same layout with the weight's fp32 bits in tf's place (those bits pass
+// the tf check below, so the two must never share a magic).
 void LexIndex::save(const char* path) {
   DeviceGuard g(device_);
   begin(stream_);
@@ -1200,7 +1410,7 @@ void LexIndex::save(const char* path) {
   std::string tmp = std::string(path) + ".tmp";
   FILE* f = std::fopen(tmp.c_str(), "wb");
   if (!f) throw Error(SR_ERR_IO, std::string("lex.save: cannot open ") + path);
-  bool ok = std::fwrite("SRMILEX1", 1, 8, f) == 8;
+  bool ok = std::fwrite(mode_ == SR_LEX_IMPACT ? "SRMILEX2" : "SRMILEX1", 1, 8, f) == 8;
   ok = ok && std::fwrite(&k1_, 4, 1, f) == 1 && std::fwrite(&b_, 4, 1, f) == 1;
   ok = ok && std::fwrite(&rows_, 8, 1, f) == 1 && std::fwrite(&P_, 8, 1, f) == 1;
   ok = ok && (rows_ == 0 || std::fwrite(dl_host_.data(), 4, (size_t)rows_, f) == (size_t)rows_);
@@ -1219,7 +1429,9 @@ LexIndex* LexIndex::load(const char* path, int device) {
   char magic[8];
   float k1 = 0.f, b = 0.f;
   int64_t rows = -1, P = -1;
-  bool ok = std::fread(magic, 1, 8, f) == 8 && std::memcmp(magic, "SRMILEX1", 8) == 0;
+  bool ok = std::fread(magic, 1, 8, f) == 8;
+  const bool impact = ok && std::memcmp(magic, "SRMILEX2", 8) == 0;
+  ok = ok && (impact || std::memcmp(magic, "SRMILEX1", 8) == 0);
   ok = ok && std::fread(&k1, 4, 1, f) == 1 && std::fread(&b, 4, 1, f) == 1;
   ok = ok && std::fread(&rows, 8, 1, f) == 1 && std::fread(&P, 8, 1, f) == 1 && rows >= 0 && P >= 0 &&
        rows < (int64_t(1) << 31) && P < (int64_t(1) << 40) && std::isfinite(k1) && std::isfinite(b);
@@ -1253,12 +1465,18 @@ LexIndex* LexIndex::load(const char* path, int device) {
   for (int64_t i = 0; i < P && ok; ++i) {
     const int64_t row = (int64_t)(fv[(size_t)i] >> 32);
     const uint32_t tf = (uint32_t)(fv[(size_t)i] & 0xffffffffu);
-    ok = ft[(size_t)i] >= 0 && ft[(size_t)i] < kLexMaxVocab && row < rows && row >= prev && tf >= 1 &&
-         tf < (1u << 31);
+    ok = ft[(size_t)i] >= 0 && ft[(size_t)i] < kLexMaxVocab && row < rows && row >= prev;
+    if (impact) {
+      float w;
+      std::memcpy(&w, &tf, 4);
+      ok = ok && std::isfinite(w) && w > 0.f && w <= SR_IMPACT_MAX_WEIGHT;
+    } else {
+      ok = ok && tf >= 1 && tf < (1u << 31);
+    }
     prev = row;
   }
   if (!ok) throw Error(SR_ERR_IO, std::string("lex.load: corrupt postings in ") + path);
-  LexIndex* x = new LexIndex(device, k1, b);
+  LexIndex* x = new LexIndex(device, k1, b, impact ? SR_LEX_IMPACT : SR_LEX_BM25);
   try {
     x->load_rows(dl, live, ft, fv);
   } catch (...) {

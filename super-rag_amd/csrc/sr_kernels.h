@@ -140,6 +140,15 @@ void launch_layernorm(const void* y, bool y_f16, const float* gamma, const float
                       int M, int d, half_t* h16, float* h32, hipStream_t s);
 void launch_pool_l2(const void* h, bool h_f16, const int32_t* mask, int B, int S, int d, int pool,
                     void* out, int out_dtype, int ld_out, hipStream_t s);
+// sparse head: tw[t] = max(0, h[t] . w + bias) where mask[t] != 0, else 0 (h: M x d final states)
+void launch_sparse_token_weights(const void* h, bool h_f16, const int32_t* mask, const float* w,
+                                 const float* bias, int M, int d, float* tw, hipStream_t s);
+// token -> term collapse of B sequences of S tokens (device ids / mask / tw, host special_ids):
+// out_terms / out_weights B x S (-1 / 0 past the count), out_count B
+void sparse_terms_check_args(int B, int S, int n_special);
+void launch_sparse_terms(const int32_t* ids, const int32_t* mask, const float* tw, int B, int S,
+                         const int32_t* special_ids, int n_special, int32_t* out_terms,
+                         float* out_weights, int32_t* out_count, hipStream_t s);
 void launch_cls_logits(const float* t, const float* w, const float* bias, int P, int d,
                        int labels, float* out, hipStream_t s);
 void launch_normalize_rows(const void* x, int dtype, int64_t n, int dim, half_t* out, int ld,

@@ -225,9 +225,25 @@ class Encoder {
   void set_weight(const std::string& name, const float* data, int64_t numel);
   std::string missing() const;  // empty when every weight is set
 
+  // forward_dev's "keep all tokens" request (mode 0 only): the sparse head's outputs, computed from
+  // the final states of every token, so the last layer runs in full whatever the pooling.
+  struct SparseOut {
+    const int32_t* special_ids;   // host, n_special in [0, 16]
+    int n_special;
+    float* tok_weight;            // B x S device, may be null
+    int32_t* terms;               // B x S device
+    float* weights;               // B x S device
+    int32_t* count;               // B device
+  };
   // mode 0: pooled embeddings to `out` (dtype/ld_out); mode 1: classifier logits (fp32).
   void forward_dev(const int32_t* ids, const int32_t* mask, const int32_t* types, int B, int S,
-                   int mode, int pool, void* out, int out_dtype, int ld_out, hipStream_t s);
+                   int mode, int pool, void* out, int out_dtype, int ld_out, hipStream_t s,
+                   const SparseOut* sparse = nullptr);
+  // host buffers, blocking: the dense embedding (fp32 B x hidden) and the sparse outputs
+  void forward_sparse_host(const int32_t* ids, const int32_t* mask, const int32_t* types, int B, int S,
+                           int pool, float* out_dense, const int32_t* special_ids, int n_special,
+                           float* out_tok_weight, int32_t* out_terms, float* out_weights,
+                           int32_t* out_count);
   void forward_host(const int32_t* ids, const int32_t* mask, const int32_t* types, int B, int S,
                     int mode, int pool, float* out);
 
@@ -277,6 +293,10 @@ class Encoder {
   std::map<std::string, bool> is_set_;
   // workspace
   DevBuf ids_, mask_, types_, pos_, h16_, h32_, qkv_, ctx_, y32_, ffn_, clst_, hostio_;
+  // sparse head (optional: "sparse_linear.weight" [hidden], "sparse_linear.bias" [1], fp32) and the
+  // token weights of one call when the caller wants none
+  DevBuf sparse_w_, sparse_b_, sparse_tw_;
+  bool sparse_w_set_ = false, sparse_b_set_ = false;
   DevBuf statA_, statB_, mrA_, mrB_;  // per-row LayerNorm partials / (mu, rstd) (folded path)
   bool fold_ready_ = false;  // folded weights match the current weights
   int fp8_ = 0;
@@ -292,11 +312,31 @@ class Encoder {
 };
 
 // ------------------------------------------------------------------------------------------------
-// BM25 lexical index over the rows of a store (k_lex.hip).
+// Lexical index over the rows of a store (k_lex.hip): BM25 (a posting carries tf), or impact
+// (SR_LEX_IMPACT: a posting carries the fp32 bits of a learned document weight in tf's place and a
+// row's score is the fixed-point dot product with the query's weights).
 class LexIndex {
  public:
-  LexIndex(int device, float k1, float b);
+  LexIndex(int device, float k1, float b, int mode = SR_LEX_BM25);
   ~LexIndex();
+
+  int mode() const { return mode_; }
+  // one scored term of one query: its multiplicity (BM25) and idf (BM25) or query weight (impact)
+  struct QTerm {
+    int32_t term, mult;
+    float w;
+  };
+  // impact mode.  n documents: terms[off[i] .. off[i+1]) distinct term ids with weights in
+  // (0, SR_IMPACT_MAX_WEIGHT]
+  void add_weighted(const int64_t* off, const int32_t* terms, const float* weights, int64_t n,
+                    int64_t* first_row);
+  // query b: terms qterms[qoff[b] .. qoff[b+1]) with weights >= 0 (a repeated id keeps its maximum)
+  void search_weighted_host(const int64_t* qoff, const int32_t* qterms, const float* qweights, int B,
+                            int k, const uint8_t* allow, int64_t mask_key, float* out_score,
+                            int64_t* out_rows, uint32_t* out_fixed);
+  void score_rows_weighted_host(const int64_t* qoff, const int32_t* qterms, const float* qweights,
+                                int B, const int64_t* rows, int K, float* out_score,
+                                uint32_t* out_fixed);
 
   // n documents: terms[off[i] .. off[i+1]) distinct term ids with frequencies tf, length dl[i]
   void add(const int64_t* off, const int32_t* terms, const int32_t* tf, const int32_t* dl,
@@ -345,6 +385,19 @@ class LexIndex {
  private:
   void rebuild(hipStream_t s);
   const uint8_t* eligibility(const uint8_t* allow, int64_t mask_key, hipStream_t s);
+  // add / add_weighted after their checks: upload n rows of validated postings
+  void append(const int64_t* off, const int32_t* terms, const uint64_t* val, const int32_t* dl,
+              int64_t n);
+  // search_dev / search_weighted_host after the query preparation (between begin and end, rebuilt)
+  void search_terms(const std::vector<std::vector<QTerm>>& qt, int k, const uint8_t* elig, float adl,
+                    float* out_score, int64_t* out_rows, hipStream_t s, int64_t row_offset,
+                    uint32_t* out_fixed);
+  // score_rows_dev / score_rows_weighted_host likewise (qt sorted by term id inside a query)
+  void score_rows_terms(const std::vector<std::vector<QTerm>>& qt, const int64_t* rows, int K,
+                        int64_t row_offset, float adl, float miss, float* out_score,
+                        uint32_t* out_fixed, hipStream_t s);
+  std::vector<std::vector<QTerm>> weighted_query_terms(const int64_t* qoff, const int32_t* qterms,
+                                                       const float* qweights, int B) const;
   static float idf(int64_t df, int64_t n_live);
   static float avgdl(int64_t sum_dl, int64_t n_live);
   void forward(std::vector<int32_t>& fterm, std::vector<uint64_t>& fval);
@@ -353,6 +406,7 @@ class LexIndex {
 
   int device_;
   float k1_, b_;
+  int mode_;
   hipStream_t stream_ = nullptr;
   hipEvent_t done_ = nullptr;
   int64_t rows_ = 0, live_n_ = 0, P_ = 0, vocab_ = 0, nnz_ = 0, sum_dl_ = 0, max_df_ = 0;

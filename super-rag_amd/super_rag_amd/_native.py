@@ -35,6 +35,9 @@ SR_GROUP_MAX_SIZE = 8
 SR_FUSE_MINMAX = 0
 SR_FUSE_FLOOR = 1
 SR_FUSE_FLOOR_FULL = 2
+SR_LEX_BM25 = 0
+SR_LEX_IMPACT = 1
+SR_IMPACT_MAX_WEIGHT = 16.0
 
 
 class NativeUnavailableError(RuntimeError):
@@ -177,6 +180,21 @@ SIGNATURES = {
                                   c_void_p, c_void_p]),
     "sr_lex_score_rows_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p,
                                       c_int64, c_void_p, c_void_p, c_void_p]),
+    "sr_lex_create_impact": (c_int, [c_int, POINTER(c_void_p)]),
+    "sr_lex_scoring": (c_int, [c_void_p, P_I32]),
+    "sr_lex_add_weighted": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, P_I64]),
+    "sr_lex_search_weighted": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                       c_int64, c_void_p, c_void_p, c_void_p]),
+    "sr_lex_score_rows_weighted": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                           c_int, c_void_p, c_void_p]),
+    "sr_sparse_terms_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p,
+                                    c_void_p, c_void_p, c_int, c_void_p]),
+    "sr_encoder_forward_sparse_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                              c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                              c_void_p, c_void_p, c_void_p]),
+    "sr_encoder_forward_sparse": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                          c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                          c_void_p]),
     "sr_score_fuse_sides": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
                                     c_void_p, c_int, c_int, c_float, c_float, c_float, c_float, c_int,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_int]),

@@ -80,6 +80,34 @@ class EmbeddingService:
             raise EmbeddingError(f"Embedding API error: {e}",
                                  {"provider": self.embedding_provider, "model": self.model}) from e
 
+    def embed_sparse(self, texts: List[str]):
+        """Dense and learned-sparse vectors of ``texts`` from ONE forward pass each (bge-m3's
+        multi-function output) -> (dense rows as embed_documents, [{token_id: weight}] per text).
+        The sparse vector has one weight per distinct token id of the text, none for the spec's
+        bos / eos / pad / unk; it is what NativeImpactIndex.add / search take.  Needs an encoder
+        with a sparse head (a model directory holding sparse_linear.pt, or set_sparse_head)."""
+        if not texts:
+            raise EmptyTextError(0)
+        if not getattr(self.encoder, "has_sparse_head", False):
+            raise EmbeddingError(f"model {self.model} has no sparse head (sparse_linear.pt)",
+                                 {"provider": self.embedding_provider, "model": self.model})
+        clean = [t.replace("\n", " ") if t and t.strip() else " " for t in texts]
+        order = sorted(range(len(clean)), key=lambda i: len(clean[i]))
+        dense = np.empty((len(clean), self.dimension), dtype=np.float32)
+        sparse: List[dict] = [{} for _ in clean]
+        for s in range(0, len(order), self.device_batch):
+            idx = order[s:s + self.device_batch]
+            try:
+                ids, mask = self.tokenizer.encode_batch([clean[i] for i in idx])
+                with device_gate(getattr(self.encoder, "device", 0), "embed"):
+                    d, sp = self.encoder.embed_sparse(ids, mask)
+            except Exception as e:  # noqa: BLE001 - a failed device batch, as in _embed_with
+                raise BatchProcessingError(batch_size=len(idx), reason=f"device batch failed: {e}") from e
+            dense[idx] = d
+            for i, (t, w) in zip(idx, sp):
+                sparse[i] = dict(zip(t.tolist(), w.tolist()))
+        return dense.tolist(), sparse
+
     async def aembed_documents(self, contents: List[str]) -> List[List[float]]:
         return await asyncio.to_thread(self.embed_documents, contents)
 

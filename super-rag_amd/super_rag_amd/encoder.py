@@ -65,6 +65,7 @@ class ModelSpec:
     pad_id: int = 0
     max_length: int = 512
     residual_fp16: bool = False  # fp16 residual stream (rerankers: ranking fidelity, less traffic)
+    unk_id: int = 100            # BERT [UNK]; XLM-R <unk> = 3 (a special id of the sparse head)
     # the model directory the spec was resolved from (its checkpoint and tokenizer live there);
     # None: $SUPER_RAG_AMD_WEIGHTS/<name>
     source_dir: str | None = field(default=None, compare=False)
@@ -85,7 +86,7 @@ def _bert(name, d, L, H, F, **kw):
 
 def _xlmr(name, d, L, H, F, max_pos=514, **kw):
     return ModelSpec(name, "xlmr", 250002, d, L, H, F, max_pos, 1, 1e-5, 1, bos_id=0, eos_id=2,
-                     pad_id=1, max_length=max_pos - 2, **kw)
+                     pad_id=1, max_length=max_pos - 2, unk_id=3, **kw)
 
 
 MODELS = {
@@ -139,11 +140,11 @@ def spec_from_dir(path: str, name: str | None = None) -> ModelSpec:
             pool = "mean"
     pad = int(cfg.get("pad_token_id", 0 if arch == "bert" else 1))
     if arch == "bert":
-        bos, eos = 101, 102
-        special = ("[CLS]", "[SEP]", "[PAD]")
+        bos, eos, unk = 101, 102, 100
+        special = ("[CLS]", "[SEP]", "[PAD]", "[UNK]")
     else:
-        bos, eos = int(cfg.get("bos_token_id", 0)), int(cfg.get("eos_token_id", 2))
-        special = ("<s>", "</s>", "<pad>")
+        bos, eos, unk = int(cfg.get("bos_token_id", 0)), int(cfg.get("eos_token_id", 2)), 3
+        special = ("<s>", "</s>", "<pad>", "<unk>")
     tok = os.path.join(path, "tokenizer.json")
     if os.path.exists(tok):
         from tokenizers import Tokenizer as HFTokenizer
@@ -151,6 +152,7 @@ def spec_from_dir(path: str, name: str | None = None) -> ModelSpec:
         ids = [t.token_to_id(s) for s in special]
         bos, eos = ids[0] if ids[0] is not None else bos, ids[1] if ids[1] is not None else eos
         pad = ids[2] if ids[2] is not None else pad
+        unk = ids[3] if ids[3] is not None else unk
     max_pos = int(cfg["max_position_embeddings"])
     off = pad if arch == "xlmr" else 0
     return ModelSpec(name or os.path.basename(os.path.normpath(path)), arch, int(cfg["vocab_size"]),
@@ -160,7 +162,7 @@ def spec_from_dir(path: str, name: str | None = None) -> ModelSpec:
                      float(cfg.get("layer_norm_eps", 1e-12 if arch == "bert" else 1e-5)), off,
                      pool=pool, classifier=classifier, num_labels=num_labels, bos_id=bos,
                      eos_id=eos, pad_id=pad, max_length=max_pos - off - (1 if off else 0),
-                     residual_fp16=bool(classifier))
+                     residual_fp16=bool(classifier), unk_id=unk)
 
 
 def resolve_spec(model: str) -> ModelSpec:
@@ -299,14 +301,38 @@ def model_weights(spec: ModelSpec, checkpoint: str | None = None, seed: int = 0,
         f"explicit opt-in SUPER_RAG_AMD_SYNTHETIC=1")
 
 
+def load_sparse_head(directory: str | None, hidden: int):
+    """bge-m3's ``sparse_linear.pt`` of a model directory (a torch state dict: weight [1, hidden],
+    bias [1]) -> (weight [hidden] fp32, bias [1] fp32), or None when the directory has none."""
+    if not directory:
+        return None
+    path = os.path.join(directory, "sparse_linear.pt")
+    if not os.path.exists(path):
+        return None
+    import torch
+    sd = torch.load(path, map_location="cpu", weights_only=True)
+    try:
+        w = sd["weight"].float().numpy().reshape(-1)
+        b = sd["bias"].float().numpy().reshape(-1)
+    except (KeyError, TypeError, AttributeError) as e:
+        raise ModelAssetsError(f"{path}: not a sparse_linear state dict (weight, bias)") from e
+    if w.size != hidden or b.size != 1:
+        raise ModelAssetsError(f"{path}: weight has {w.size} values and bias {b.size}, expected "
+                               f"{hidden} and 1")
+    return w.astype(np.float32), b.astype(np.float32)
+
+
 class Encoder:
     """One encoder instance resident on one device (sr_encoder_* in the C-ABI)."""
 
     def __init__(self, spec: ModelSpec, device: int = 0, weights: dict | None = None,
                  seed: int = 0, max_tokens: int = 0, init_style: str = "hf",
                  checkpoint: str | None = None):
+        sparse = None
         if weights is None:   # resolve first: a missing checkpoint fails before any device work
             weights = model_weights(spec, checkpoint, seed, init_style)
+            sparse = load_sparse_head(os.path.dirname(checkpoint) if checkpoint else spec.asset_dir,
+                                      spec.hidden)
         N.require_gpu()
         self.spec = spec
         self.device = int(device)
@@ -318,6 +344,9 @@ class Encoder:
         N.call("sr_encoder_create", ctypes.byref(cfg), self.device, ctypes.byref(h))
         self._h = h
         self.load_weights(weights)
+        self.has_sparse_head = False
+        if sparse is not None:
+            self.set_sparse_head(*sparse)
 
     def load_weights(self, weights: dict) -> None:
         for name, v in weights.items():
@@ -327,6 +356,18 @@ class Encoder:
             a = np.ascontiguousarray(np.asarray(v, dtype=np.float32))
             N.call("sr_encoder_set_weight", self._h, name.encode(), N.ptr(a), a.size)
         N.call("sr_encoder_ready", self._h)
+
+    def set_sparse_head(self, weight, bias) -> None:
+        """bge-m3's sparse_linear: weight [hidden] (or [1, hidden]) and bias (1 value), kept fp32
+        on the device.  Optional: without it only embed_sparse* fail."""
+        w = np.ascontiguousarray(np.asarray(weight, dtype=np.float32).reshape(-1))
+        b = np.ascontiguousarray(np.asarray(bias, dtype=np.float32).reshape(-1))
+        if w.size != self.spec.hidden or b.size != 1:
+            raise ValueError(f"sparse head needs weight [{self.spec.hidden}] and bias [1], got "
+                             f"{w.size} and {b.size} values")
+        N.call("sr_encoder_set_weight", self._h, b"sparse_linear.weight", N.ptr(w), w.size)
+        N.call("sr_encoder_set_weight", self._h, b"sparse_linear.bias", N.ptr(b), b.size)
+        self.has_sparse_head = True
 
     def set_fp8(self, mode: int) -> None:
         """Opt-in fp8 precision mode (LN-folded fp16-residual encoders, e.g. cross-encoders):
@@ -363,6 +404,37 @@ class Encoder:
                N.ptr(out))
         return out
 
+    def embed_sparse(self, ids, mask, type_ids=None, pool: str | None = None,
+                     return_token_weights: bool = False, special_ids=None):
+        """One forward pass -> (dense [B, hidden] fp32, [(terms int32, weights fp32)] per sequence
+        [, token weights [B, S] fp32]): the dense embedding of embed() and bge-m3's sparse vector,
+        one weight per distinct token id (its maximum over the positions, ids in order of first
+        appearance; ``special_ids`` default to the spec's bos / eos / pad / unk and never appear).
+        sr_encoder_forward_sparse; needs set_sparse_head."""
+        ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int32))
+        mask = np.ascontiguousarray(np.asarray(mask, dtype=np.int32))
+        tt = None if type_ids is None else np.ascontiguousarray(np.asarray(type_ids, dtype=np.int32))
+        B, S = ids.shape
+        sp = self._special(special_ids)
+        dense = np.empty((B, self.spec.hidden), dtype=np.float32)
+        tw = np.empty((B, S), dtype=np.float32)
+        terms = np.empty((B, S), dtype=np.int32)
+        weights = np.empty((B, S), dtype=np.float32)
+        count = np.zeros(B, dtype=np.int32)
+        p = N.SR_POOL_CLS if (pool or self.spec.pool) == "cls" else N.SR_POOL_MEAN
+        N.call("sr_encoder_forward_sparse", self._h, N.ptr(ids), N.ptr(mask), N.ptr(tt), B, S, p,
+               N.ptr(dense), N.ptr(sp), int(sp.size), N.ptr(tw), N.ptr(terms), N.ptr(weights),
+               N.ptr(count))
+        sparse = [(terms[b, :count[b]].copy(), weights[b, :count[b]].copy()) for b in range(B)]
+        return (dense, sparse, tw) if return_token_weights else (dense, sparse)
+
+    def _special(self, special_ids) -> np.ndarray:
+        if special_ids is None:
+            s = self.spec
+            special_ids = sorted({s.bos_id, s.eos_id, s.pad_id, s.unk_id})
+        sp = np.ascontiguousarray(np.asarray(list(special_ids), dtype=np.int32).reshape(-1))
+        return sp
+
     def cross_score(self, ids, mask, type_ids=None) -> np.ndarray:
         ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int32))
         mask = np.ascontiguousarray(np.asarray(mask, dtype=np.int32))
@@ -386,6 +458,30 @@ class Encoder:
         N.call("sr_encoder_forward_dev", self._h, N.ptr(ids), N.ptr(mask), N.ptr(type_ids), B, S,
                p, N.ptr(out), dt, out.shape[1], N.stream_handle(stream))
         return out
+
+    def embed_sparse_dev(self, ids, mask, type_ids=None, out=None, ld_out: int | None = None,
+                         fp16: bool = True, pool: str | None = None,
+                         return_token_weights: bool = False, special_ids=None, stream=None):
+        """embed_sparse on device tensors (sr_encoder_forward_sparse_dev), asynchronous on
+        ``stream`` -> (dense as embed_dev, terms [B, S] int32 (-1 past the count), weights [B, S]
+        fp32, count [B] int32 [, token weights [B, S] fp32])."""
+        import torch
+        B, S = ids.shape
+        ld = ld_out or self.spec.hidden
+        if out is None:
+            out = torch.empty((B, ld), dtype=torch.float16 if fp16 else torch.float32,
+                              device=ids.device)
+        dt = N.SR_DTYPE_F16 if out.dtype == torch.float16 else N.SR_DTYPE_F32
+        p = N.SR_POOL_CLS if (pool or self.spec.pool) == "cls" else N.SR_POOL_MEAN
+        sp = self._special(special_ids)
+        terms = torch.empty((B, S), dtype=torch.int32, device=ids.device)
+        weights = torch.empty((B, S), dtype=torch.float32, device=ids.device)
+        count = torch.empty((B,), dtype=torch.int32, device=ids.device)
+        tw = torch.empty((B, S), dtype=torch.float32, device=ids.device) if return_token_weights else None
+        N.call("sr_encoder_forward_sparse_dev", self._h, N.ptr(ids), N.ptr(mask), N.ptr(type_ids), B, S,
+               p, N.ptr(out), dt, out.shape[1], N.ptr(sp), int(sp.size), N.ptr(tw), N.ptr(terms),
+               N.ptr(weights), N.ptr(count), N.stream_handle(stream))
+        return (out, terms, weights, count, tw) if return_token_weights else (out, terms, weights, count)
 
     def cross_score_dev(self, ids, mask, type_ids=None, out=None, stream=None):
         import torch

@@ -17,6 +17,10 @@ The reference declares the pieces but ships no backend: a ``fulltext_search`` no
   * ``NativeLexIndex.score_rows`` / ``ShardedLex.score_rows``: the exact BM25 of given (query, row)
     pairs (lex_score_rows), and ``fusion="floor_full"``: floor fusion with the BM25 side completed
     by it for the dense list's rows, as the dense side already is.
+  * ``NativeImpactIndex`` / ``sparse_hybrid_search``: learned-sparse retrieval, the same index in
+    its impact scoring mode (documents and queries are term ids with fp32 weights, e.g. bge-m3's
+    sparse vectors from ``Encoder.embed_sparse``; the score is their fixed-point dot product) and
+    its fusion with the dense side by the rules above.
 There is no CPU fallback: every entry point needs the HIP library and a GPU.
 """
 from __future__ import annotations
@@ -137,6 +141,10 @@ class NativeLexIndex:
         N.require_gpu()
         h = ctypes.c_void_p()
         N.call("sr_lex_load", path.encode(), int(device), ctypes.byref(h))
+        if lex_scoring(h) != N.SR_LEX_BM25:
+            N.load().sr_lex_destroy(h)
+            raise ValueError(f"{path} is an impact (learned-sparse) snapshot: load it with "
+                             "NativeImpactIndex.load")
         return cls(device, _handle=h)
 
     def close(self) -> None:
@@ -747,6 +755,155 @@ def hybrid_search(store, lex: NativeLexIndex, queries, query_terms: Sequence[Seq
            k_each, int(rank_const), float(min_score), None if a is None else N.ptr(a),
            int(mask_key), N.ptr(scores), N.ptr(rows))
     return scores, rows
+
+
+def lex_scoring(handle) -> int:
+    """SR_LEX_BM25 or SR_LEX_IMPACT of a native sr_lex handle (sr_lex_scoring)."""
+    m = ctypes.c_int32(0)
+    N.call("sr_lex_scoring", handle, ctypes.byref(m))
+    return int(m.value)
+
+
+def weighted_arrays(items):
+    """[(terms, weights) | {term: weight}] -> (off int64[n+1], terms int32, weights fp32), the C-ABI
+    layout of sr_lex_add_weighted documents and sr_lex_search_weighted queries."""
+    off = np.zeros(len(items) + 1, dtype=np.int64)
+    flat_t: list = []
+    flat_w: list = []
+    for i, it in enumerate(items):       # (one pass over Python lists: a query batch is packed per call)
+        if isinstance(it, dict):
+            t, w = list(it.keys()), list(it.values())
+        else:
+            t, w = it
+            t = t.tolist() if hasattr(t, "tolist") else list(t)
+            w = w.tolist() if hasattr(w, "tolist") else list(w)
+        if len(t) != len(w):
+            raise ValueError(f"item {i}: {len(t)} terms but {len(w)} weights")
+        flat_t += t
+        flat_w += w
+        off[i + 1] = len(flat_t)
+    if not flat_t:
+        return off, np.zeros(1, np.int32), np.ones(1, np.float32)
+    terms = np.asarray(flat_t, dtype=np.int64)
+    if terms.min() < -2**31 or terms.max() >= 2**31:
+        raise ValueError("term id outside int32")
+    return off, terms.astype(np.int32), np.asarray(flat_w, dtype=np.float32)
+
+
+class NativeImpactIndex:
+    """Learned-sparse index over the rows of a store, resident in HBM of one device: sr_lex in its
+    impact scoring mode (k_lex.hip).  A document and a query are term ids with fp32 weights (bge-m3's
+    sparse head, SPLADE, any "sparse vector"); a row's score is the dot product over shared terms in
+    2^-16 fixed point, every product rounded on its own (exact and order-independent; DESIGN.md
+    "Learned-sparse retrieval").  Document weights lie in (0, 16], query weights are >= 0."""
+
+    def __init__(self, device: int = 0, _handle=None):
+        self._h = None
+        if _handle is None:
+            N.require_gpu()
+            h = ctypes.c_void_p()
+            N.call("sr_lex_create_impact", int(device), ctypes.byref(h))
+            _handle = h
+        self._h = _handle
+        self.device = int(device)
+
+    @classmethod
+    def load(cls, path: str, device: int = 0) -> "NativeImpactIndex":
+        N.require_gpu()
+        h = ctypes.c_void_p()
+        N.call("sr_lex_load", path.encode(), int(device), ctypes.byref(h))
+        if lex_scoring(h) != N.SR_LEX_IMPACT:
+            N.load().sr_lex_destroy(h)
+            raise ValueError(f"{path} is a BM25 snapshot: load it with NativeLexIndex.load")
+        return cls(device, _handle=h)
+
+    close = NativeLexIndex.close
+    __del__ = NativeLexIndex.__del__
+    remove = NativeLexIndex.remove
+    compact = NativeLexIndex.compact
+    save = NativeLexIndex.save
+    stats = NativeLexIndex.stats
+
+    def add(self, docs) -> int:
+        """Append documents, each (terms, weights) or {term: weight} with distinct terms; returns
+        the first row id."""
+        if not len(docs):
+            return self.stats()["rows"]
+        return self.add_arrays(*weighted_arrays(docs))
+
+    def add_arrays(self, off, terms, weights) -> int:
+        """Bulk append in the C-ABI layout (weighted_arrays output)."""
+        off = np.ascontiguousarray(off, dtype=np.int64)
+        terms = np.ascontiguousarray(terms, dtype=np.int32)
+        weights = np.ascontiguousarray(weights, dtype=np.float32)
+        if terms.size == 0:
+            terms, weights = np.zeros(1, np.int32), np.ones(1, np.float32)
+        first = ctypes.c_int64(0)
+        N.call("sr_lex_add_weighted", self._h, N.ptr(off), N.ptr(terms), N.ptr(weights), len(off) - 1,
+               ctypes.byref(first))
+        return int(first.value)
+
+    def search(self, queries, k: int, allow=None, mask_key: int = 0, fixed: bool = False):
+        """Impact top-k per query ((terms, weights) or {term: weight}; a repeated id keeps its
+        maximum weight) -> (score [B,k] fp32 desc, rows [B,k] int64), -inf / -1 past the matches;
+        fixed: also the exact 2^-16 fixed-point scores [B,k] uint32."""
+        Bq = len(queries)
+        scores = np.empty((Bq, k), dtype=np.float32)
+        rows = np.empty((Bq, k), dtype=np.int64)
+        fx = np.zeros((Bq, k), dtype=np.uint32) if fixed else None
+        if Bq:
+            qoff, qterms, qw = weighted_arrays(queries)
+            a = None if allow is None else _mask(allow, self.stats()["rows"])
+            N.call("sr_lex_search_weighted", self._h, N.ptr(qoff), N.ptr(qterms), N.ptr(qw), Bq, int(k),
+                   None if a is None else N.ptr(a), int(mask_key), N.ptr(scores), N.ptr(rows),
+                   N.ptr(fx) if fixed else None)
+        return (scores, rows, fx) if fixed else (scores, rows)
+
+    def score_rows(self, queries, rows, fixed: bool = False):
+        """Exact impact score of given (query, row) pairs (sr_lex_score_rows_weighted): rows [B, K]
+        int64 -> score [B, K] fp32, the score search gives that row: -inf for a row < 0, past the
+        index or tombstoned, 0 for a live row that shares no scored term."""
+        Bq = len(queries)
+        r = np.ascontiguousarray(np.asarray(rows, dtype=np.int64))
+        if r.ndim != 2 or r.shape[0] != Bq:
+            raise ValueError(f"rows must be [{Bq}, K], got {r.shape}")
+        score = np.empty(r.shape, dtype=np.float32)
+        fx = np.zeros(r.shape, dtype=np.uint32) if fixed else None
+        if r.size:
+            qoff, qterms, qw = weighted_arrays(queries)
+            N.call("sr_lex_score_rows_weighted", self._h, N.ptr(qoff), N.ptr(qterms), N.ptr(qw), Bq,
+                   N.ptr(r), r.shape[1], N.ptr(score), N.ptr(fx) if fixed else None)
+        return (score, fx) if fixed else score
+
+
+def sparse_hybrid_search(store, index: NativeImpactIndex, q, q_sparse, k: int,
+                         k_each: Optional[int] = None, fusion: str = "rrf", alpha: float = 0.5,
+                         min_score: float = float("-inf"), allow=None, mask_key: int = 0,
+                         rank_const: int = 1):
+    """Dense + learned-sparse retrieval: dense top-k_each (store.search_sim) and impact top-k_each
+    (index.search of ``q_sparse``), fused on the device by hybrid_search's rules with the impact
+    score in BM25's place.  "rrf" -> (rrf score [B,k] fp64, rows); "relative": min-max of each
+    list; "floor": floor_a = -1, floor_b = 0 and the dense side completed with the exact cosines
+    of the sparse list's rows; "floor_full": also the sparse side completed with the exact impact
+    scores of the dense list's rows, an exact 0 passed as unknown -> (fused [B,k] fp32, rows)."""
+    mode = fusion_mode(fusion)
+    qd = np.ascontiguousarray(np.asarray(q, dtype=np.float32))
+    if qd.ndim == 1:
+        qd = qd[None]
+    if len(q_sparse) != qd.shape[0]:
+        raise ValueError(f"{qd.shape[0]} dense queries but {len(q_sparse)} sparse ones")
+    k_each = int(k_each or k)
+    sims, dense = store.search_sim(qd, k_each, allow=allow, mask_key=mask_key)
+    ssc, sparse = index.search(q_sparse, k_each, allow=allow, mask_key=mask_key)
+    if mode is None:
+        return rrf_fuse(dense, sparse, k, rank_const, min_score, index.device)
+    check_alpha(alpha)
+    full = mode == N.SR_FUSE_FLOOR_FULL
+    side_a = store.score_rows(qd, sparse) if (mode == N.SR_FUSE_FLOOR or full) else None
+    side_b = unknown_where_zero(index.score_rows(q_sparse, dense)) if full else None
+    score, rows, _, _ = score_fuse(sims, dense, ssc, sparse, k, N.SR_FUSE_FLOOR if full else mode,
+                                   alpha, side_a, -1.0, 0.0, min_score, index.device, side_b=side_b)
+    return score, rows
 
 
 _rrf_impl = [lambda a, b, k, rc, ms, dev: rrf_fuse(a, b, k, rc, ms, dev)]
