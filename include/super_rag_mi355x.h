@@ -403,6 +403,55 @@ int sr_lex_score_rows_weighted(sr_lex* x, const int64_t* qoff, const int32_t* qt
                                const float* qweights, int B, const int64_t* rows, int K,
                                float* out_score, uint32_t* out_fixed);
 
+/* ------------------------------------------------------------------------------------------------
+ * Multi-vector (late interaction, ColBERT) index (multivec.hip, k_multivec.hip; DESIGN.md
+ * "Multi-vector retrieval"): per row of a collection the list of its token vectors (bge-m3's
+ * multi-vector output; Qdrant / Vespa / Milvus "multi-vector"), row-aligned with the store like
+ * sr_lex: row i of the index is row i of the collection.  One fp16 token pool [n_tokens, dim] in HBM,
+ * an int64 offsets array and live flags.  Score of a query (Lq >= 1 vectors q_i) against a row (Ld
+ * >= 1 vectors d_j), MaxSim:
+ *   score = (1 / Lq) sum_i max_j (q_i . d_j)
+ * on the fp16 values as stored, fp32 accumulation (v_mfma_f32_16x16x32_f16), the sum over i in a
+ * fixed order, one division.  |score - exact| <= (dim + Lq) 2^-23 max||q_i|| max||d_j||.  A pair's
+ * bits depend on the pair alone: not on B, K, its position, the other candidates, or how the row was
+ * added.  out_score[b, k] is -inf when rows[b, k] is < 0, past the index, removed or holds 0 tokens,
+ * and when q_len[b] == 0; a row may repeat within a query.
+ * Limits, SR_ERR_INVALID before any device work: dim a multiple of 64, <= 1024; K in [1, SR_MAX_TOPK];
+ * ld_q >= 1; q_len[b] in [0, min(ld_q, SR_MV_MAX_QUERY_TOKENS)] (checked by the host variant; the
+ * device variant cannot read it without a synchronisation and clamps it to that range); B == 0 is a
+ * no-op.
+ *   sr_mv_add       n rows, row i = the tokens vecs[off[i] .. off[i+1]) x dim (fp32 host, rounded to
+ *                   nearest fp16; off[0] == 0); a row may hold 0 tokens; first_row (optional) receives
+ *                   the first new row id.  Blocking.
+ *   sr_mv_add_dev   n rows, row i = the first len[i] tokens of vecs[i] (fp16 [n, ld_tok, dim] and len
+ *                   int32 [n], device: what sr_encoder_forward_multivec_dev writes).  Reads the lengths
+ *                   back to size the pool: synchronises `stream`, and has finished when it returns.
+ *   sr_mv_remove    tombstones rows (in range; twice is harmless); the tokens stay in the pool.
+ *   sr_mv_get       row's tokens as fp32 (the stored fp16 values) into out (room for cap tokens; at
+ *                   most cap are written); n_tok receives the row's count.
+ *   sr_mv_score_rows_dev  q fp16 [B, ld_q, dim], q_len int32 [B], rows int64 [B, K], out_score fp32
+ *                   [B, K], all device; the query rows at and past q_len[b] are never read.
+ *                   Asynchronous on `stream`.
+ *   sr_mv_score_rows      the same on host buffers, q fp32 rounded to nearest fp16.  Blocking.
+ * Not provided: snapshots and compaction, a multi-device variant, a whole-corpus MaxSim scan, fp8
+ * token vectors, a fused rerank entry point (multivec.m3_rerank composes the existing ones).
+ * ---------------------------------------------------------------------------------------------- */
+#define SR_MV_MAX_QUERY_TOKENS 512
+typedef struct sr_mv sr_mv;
+
+int sr_mv_create(int dim, int device, sr_mv** out);
+int sr_mv_add(sr_mv* x, const int64_t* off, const float* vecs, int64_t n, int64_t* first_row);
+int sr_mv_add_dev(sr_mv* x, const void* vecs, const int32_t* len, int64_t n, int ld_tok,
+                  int64_t* first_row, void* stream);
+int sr_mv_remove(sr_mv* x, const int64_t* rows, int64_t n);
+int sr_mv_stats(sr_mv* x, int64_t* n_rows, int64_t* n_live, int64_t* n_tokens);
+int sr_mv_get(sr_mv* x, int64_t row, float* out, int64_t cap, int64_t* n_tok);
+int sr_mv_score_rows_dev(sr_mv* x, const void* q, const int32_t* q_len, int B, int ld_q,
+                         const int64_t* rows, int K, float* out_score, void* stream);
+int sr_mv_score_rows(sr_mv* x, const float* q, const int32_t* q_len, int B, int ld_q,
+                     const int64_t* rows, int K, float* out_score);
+void sr_mv_destroy(sr_mv* x);
+
 /* Reciprocal-rank fusion of two ranked row lists per query (B x ka and B x kb, -1 padded), as
  * graphiti rrf (graphiti_core/search/search_utils.py:1762-1778): score = sum 1 / (rank +
  * rank_const) in fp64, order (score desc, first appearance), rows with score < min_score
@@ -592,6 +641,41 @@ int sr_encoder_forward_sparse(sr_encoder* e, const int32_t* ids, const int32_t* 
                               const int32_t* type_ids, int B, int S, int pool, float* out_dense,
                               const int32_t* special_ids, int n_special, float* out_tok_weight,
                               int32_t* out_terms, float* out_weights, int32_t* out_count);
+/* The multi-vector (ColBERT) head of a multi-function embedder (bge-m3's colbert_linear;
+ * k_encoder_misc.hip colbert_pack, DESIGN.md "Multi-vector retrieval").  sr_encoder_set_weight accepts
+ * "colbert_linear.weight" (dc * hidden values, row-major [dc, hidden]; dc is inferred from the count
+ * and must be a multiple of 128, <= 1024; kept fp16) and "colbert_linear.bias" (dc values, fp32).
+ * Optional like the sparse head: sr_encoder_ready and every other call behave the same with or
+ * without them, and the calls below return SR_ERR_STATE (naming the missing one) until both are set.
+ * The weight defines dc (a weight of another dc unsets the bias); the bias is set after it
+ * (SR_ERR_STATE before) and holds dc values; any other count is SR_ERR_INVALID.
+ * sr_encoder_colbert_dim gives dc, 0 without the weight.
+ *   v[b, s] = W h[b, s] + bias (fp16 operands, fp32 accumulation, rounded to fp16),
+ *   u[b, s] = v / max(||v||, 1e-12) (fp32 norm, rounded to fp16);
+ *   the multi-vector of sequence b is u[b, s] over the positions s >= 1 with mask[b, s] != 0, in
+ *   position order: position 0 (CLS / <s>) is always dropped, the closing separator stays.
+ * sr_encoder_forward_multivec_dev is ONE forward pass giving the dense embedding (out_dense /
+ * out_dtype / ld_out as in sr_encoder_forward_dev; the last layer runs in full, so SR_POOL_MEAN equals
+ * sr_encoder_forward_dev bit for bit and SR_POOL_CLS equals sr_encoder_forward_sparse_dev's), out_vecs
+ * (fp16, B x S x dc device: rows [0, out_len[b]) of sequence b the compacted unit vectors, the rows
+ * behind them zero) and out_len (B int32 device): the layout sr_mv_add_dev takes.  The sparse outputs of
+ * sr_encoder_forward_sparse_dev are one optional group: out_terms, out_weights and out_count all NULL
+ * (then special_ids and n_special are ignored and out_tok_weight must be NULL too), or all set
+ * (out_tok_weight stays optional); a half-given group is SR_ERR_INVALID.  S in [1, 8192].
+ * sr_encoder_forward_multivec takes and fills host buffers (out_dense B x hidden fp32, out_vecs B x S
+ * x dc fp32 holding the fp16 values) and blocks. */
+int sr_encoder_colbert_dim(sr_encoder* e, int* out);
+int sr_encoder_forward_multivec_dev(sr_encoder* e, const int32_t* ids, const int32_t* mask,
+                                    const int32_t* type_ids, int B, int S, int pool, void* out_dense,
+                                    int out_dtype, int ld_out, void* out_vecs, int32_t* out_len,
+                                    const int32_t* special_ids, int n_special, float* out_tok_weight,
+                                    int32_t* out_terms, float* out_weights, int32_t* out_count,
+                                    void* stream);
+int sr_encoder_forward_multivec(sr_encoder* e, const int32_t* ids, const int32_t* mask,
+                                const int32_t* type_ids, int B, int S, int pool, float* out_dense,
+                                float* out_vecs, int32_t* out_len, const int32_t* special_ids,
+                                int n_special, float* out_tok_weight, int32_t* out_terms,
+                                float* out_weights, int32_t* out_count);
 /* Cross-encoder relevance: P (query, passage) pairs already packed as token ids (P x S);
  * out_logits: P x num_labels fp32 raw logits (bge-reranker scores = logits, sigmoid optional). */
 int sr_cross_score(sr_encoder* e, const int32_t* ids, const int32_t* mask,

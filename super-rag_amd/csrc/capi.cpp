@@ -21,6 +21,9 @@ struct sr_lex {
 struct sr_store_set {
   sr::StoreSet* impl;
 };
+struct sr_mv {
+  sr::MultiVecIndex* impl;
+};
 
 namespace sr {
 
@@ -1170,8 +1173,10 @@ int sr_encoder_forward_sparse_dev(sr_encoder* e, const int32_t* ids, const int32
   if (n_special > 0) SR_NONNULL(special_ids);
   std::lock_guard<std::mutex> lk(e->impl->mu);
   const sr::Encoder::SparseOut so{special_ids, n_special, out_tok_weight, out_terms, out_weights, out_count};
+  sr::Encoder::TokenHeads th;
+  th.sparse = &so;
   e->impl->forward_dev(ids, mask, type_ids, B, S, 0, pool, out_dense, out_dtype, ld_out,
-                       reinterpret_cast<hipStream_t>(stream), &so);
+                       reinterpret_cast<hipStream_t>(stream), &th);
   SR_API_END
 }
 
@@ -1186,6 +1191,139 @@ int sr_encoder_forward_sparse(sr_encoder* e, const int32_t* ids, const int32_t* 
   e->impl->forward_sparse_host(ids, mask, type_ids, B, S, pool, out_dense, special_ids, n_special,
                                out_tok_weight, out_terms, out_weights, out_count);
   SR_API_END
+}
+
+int sr_encoder_colbert_dim(sr_encoder* e, int* out) {
+  SR_API_BEGIN
+  SR_NONNULL(e);
+  SR_NONNULL(out);
+  std::lock_guard<std::mutex> lk(e->impl->mu);
+  *out = e->impl->colbert_dim();
+  SR_API_END
+}
+
+int sr_encoder_forward_multivec_dev(sr_encoder* e, const int32_t* ids, const int32_t* mask,
+                                    const int32_t* type_ids, int B, int S, int pool, void* out_dense,
+                                    int out_dtype, int ld_out, void* out_vecs, int32_t* out_len,
+                                    const int32_t* special_ids, int n_special, float* out_tok_weight,
+                                    int32_t* out_terms, float* out_weights, int32_t* out_count,
+                                    void* stream) {
+  SR_API_BEGIN
+  SR_NONNULL(e);
+  const bool any_sparse = out_tok_weight || out_terms || out_weights || out_count;
+  const bool with_sparse = out_terms && out_weights && out_count;
+  SR_CHECK(!any_sparse || with_sparse,
+           "encoder: the sparse outputs are one group: terms, weights and count together or none");
+  if (B > 0) {
+    SR_NONNULL(ids);
+    SR_NONNULL(mask);
+    SR_NONNULL(out_dense);
+    SR_NONNULL(out_vecs);
+    SR_NONNULL(out_len);
+  }
+  if (with_sparse && n_special > 0) SR_NONNULL(special_ids);
+  std::lock_guard<std::mutex> lk(e->impl->mu);
+  const sr::Encoder::SparseOut so{special_ids, n_special, out_tok_weight, out_terms, out_weights, out_count};
+  const sr::Encoder::MultiVecOut mo{reinterpret_cast<sr::half_t*>(out_vecs), out_len};
+  sr::Encoder::TokenHeads th;
+  th.sparse = with_sparse ? &so : nullptr;
+  th.multivec = &mo;
+  e->impl->forward_dev(ids, mask, type_ids, B, S, 0, pool, out_dense, out_dtype, ld_out,
+                       reinterpret_cast<hipStream_t>(stream), &th);
+  SR_API_END
+}
+
+int sr_encoder_forward_multivec(sr_encoder* e, const int32_t* ids, const int32_t* mask,
+                                const int32_t* type_ids, int B, int S, int pool, float* out_dense,
+                                float* out_vecs, int32_t* out_len, const int32_t* special_ids,
+                                int n_special, float* out_tok_weight, int32_t* out_terms,
+                                float* out_weights, int32_t* out_count) {
+  SR_API_BEGIN
+  SR_NONNULL(e);
+  if (out_terms && n_special > 0) SR_NONNULL(special_ids);
+  std::lock_guard<std::mutex> lk(e->impl->mu);
+  e->impl->forward_multivec_host(ids, mask, type_ids, B, S, pool, out_dense, out_vecs, out_len,
+                                 special_ids, n_special, out_tok_weight, out_terms, out_weights,
+                                 out_count);
+  SR_API_END
+}
+
+// ---- multi-vector index ----------------------------------------------------------------------
+int sr_mv_create(int dim, int device, sr_mv** out) {
+  SR_API_BEGIN
+  SR_NONNULL(out);
+  *out = nullptr;
+  SR_CHECK(dim >= 64 && dim <= 1024 && dim % 64 == 0, "mv: dim must be a multiple of 64, <= 1024");
+  auto* x = new sr_mv{new sr::MultiVecIndex(dim, device)};
+  *out = x;
+  SR_API_END
+}
+
+int sr_mv_add(sr_mv* x, const int64_t* off, const float* vecs, int64_t n, int64_t* first_row) {
+  SR_API_BEGIN
+  SR_NONNULL(x);
+  std::lock_guard<std::mutex> lk(x->impl->mu);
+  x->impl->add_host(off, vecs, n, first_row);
+  SR_API_END
+}
+
+int sr_mv_add_dev(sr_mv* x, const void* vecs, const int32_t* len, int64_t n, int ld_tok,
+                  int64_t* first_row, void* stream) {
+  SR_API_BEGIN
+  SR_NONNULL(x);
+  std::lock_guard<std::mutex> lk(x->impl->mu);
+  x->impl->add_dev(reinterpret_cast<const sr::half_t*>(vecs), len, n, ld_tok, first_row,
+                   reinterpret_cast<hipStream_t>(stream));
+  SR_API_END
+}
+
+int sr_mv_remove(sr_mv* x, const int64_t* rows, int64_t n) {
+  SR_API_BEGIN
+  SR_NONNULL(x);
+  std::lock_guard<std::mutex> lk(x->impl->mu);
+  x->impl->remove(rows, n);
+  SR_API_END
+}
+
+int sr_mv_stats(sr_mv* x, int64_t* n_rows, int64_t* n_live, int64_t* n_tokens) {
+  SR_API_BEGIN
+  SR_NONNULL(x);
+  std::lock_guard<std::mutex> lk(x->impl->mu);
+  x->impl->stats(n_rows, n_live, n_tokens);
+  SR_API_END
+}
+
+int sr_mv_get(sr_mv* x, int64_t row, float* out, int64_t cap, int64_t* n_tok) {
+  SR_API_BEGIN
+  SR_NONNULL(x);
+  std::lock_guard<std::mutex> lk(x->impl->mu);
+  x->impl->get(row, out, cap, n_tok);
+  SR_API_END
+}
+
+int sr_mv_score_rows_dev(sr_mv* x, const void* q, const int32_t* q_len, int B, int ld_q,
+                         const int64_t* rows, int K, float* out_score, void* stream) {
+  SR_API_BEGIN
+  SR_NONNULL(x);
+  std::lock_guard<std::mutex> lk(x->impl->mu);
+  x->impl->score_rows_dev(reinterpret_cast<const sr::half_t*>(q), q_len, B, ld_q, rows, K, out_score,
+                          reinterpret_cast<hipStream_t>(stream));
+  SR_API_END
+}
+
+int sr_mv_score_rows(sr_mv* x, const float* q, const int32_t* q_len, int B, int ld_q,
+                     const int64_t* rows, int K, float* out_score) {
+  SR_API_BEGIN
+  SR_NONNULL(x);
+  std::lock_guard<std::mutex> lk(x->impl->mu);
+  x->impl->score_rows_host(q, q_len, B, ld_q, rows, K, out_score);
+  SR_API_END
+}
+
+void sr_mv_destroy(sr_mv* x) {
+  if (!x) return;
+  delete x->impl;
+  delete x;
 }
 
 int sr_cross_score(sr_encoder* e, const int32_t* ids, const int32_t* mask, const int32_t* type_ids,

@@ -15,8 +15,9 @@
 // classification head the last layer is computed for the CLS rows only.
 // Embedding mode pools (CLS / masked mean) and L2-normalises (K7); cross-encoder mode applies the
 // RoBERTa classification head: tanh(GEMM(h16[CLS rows], Wc) + bc) (fp32) . Wout + bout (K4 + K8).
-// With a sparse-head request (forward_dev's SparseOut) the last layer runs for every token and the
-// final states also feed sparse_token_weights and sparse_terms (k_encoder_misc.hip), per chunk.
+// With a token-heads request (forward_dev's TokenHeads) the last layer runs for every token and the
+// final states also feed the sparse head (sparse_token_weights, sparse_terms) and / or the
+// multi-vector head (a bias GEMM, then colbert_pack), per chunk (k_encoder_misc.hip).
 #include <algorithm>
 #include <cstdlib>
 #include <vector>
@@ -144,6 +145,40 @@ void Encoder::set_weight(const std::string& name, const float* data, int64_t num
     buf.reserve((size_t)want * sizeof(float));
     SR_HIP(hipMemcpy(buf.p, data, (size_t)want * sizeof(float), hipMemcpyHostToDevice));
     (is_w ? sparse_w_set_ : sparse_b_set_) = true;
+    return;
+  }
+  if (name == "colbert_linear.weight" || name == "colbert_linear.bias") {
+    // the optional multi-vector head: W [dc, hidden] fp16 (the GEMM's W layout), bias [dc] fp32;
+    // dc comes from the weight's count.  Never part of missing() / sr_encoder_ready
+    const bool is_w = name == "colbert_linear.weight";
+    SR_CHECK(data != nullptr, "encoder: null weight data");
+    if (is_w) {
+      const int64_t dc = numel / cfg_.hidden;
+      SR_CHECK(numel > 0 && numel % cfg_.hidden == 0 && dc % 128 == 0 && dc <= 1024,
+               "encoder: weight '" + name + "' has " + std::to_string(numel) +
+                   " elements, expected dc * hidden with dc a multiple of 128, <= 1024");
+    } else {
+      // the weight defines dc: the bias follows it
+      if (!colbert_w_set_) throw Error(SR_ERR_STATE, "encoder: weight not set: colbert_linear.weight");
+      SR_CHECK(numel == colbert_dc_, "encoder: weight '" + name + "' has " + std::to_string(numel) +
+                                         " elements, expected " + std::to_string(colbert_dc_));
+    }
+    DeviceGuard g(device_);
+    begin(stream_);
+    SR_HIP(hipStreamSynchronize(stream_));
+    if (is_w) {
+      std::vector<half_t> h((size_t)numel);
+      for (int64_t i = 0; i < numel; ++i) h[i] = (half_t)data[i];
+      colbert_w_.reserve(h.size() * sizeof(half_t));
+      SR_HIP(hipMemcpy(colbert_w_.p, h.data(), h.size() * sizeof(half_t), hipMemcpyHostToDevice));
+      if (colbert_dc_ != (int)(numel / cfg_.hidden)) colbert_b_set_ = false;  // a head of another width
+      colbert_dc_ = (int)(numel / cfg_.hidden);
+      colbert_w_set_ = true;
+    } else {
+      colbert_b_.reserve((size_t)numel * sizeof(float));
+      SR_HIP(hipMemcpy(colbert_b_.p, data, (size_t)numel * sizeof(float), hipMemcpyHostToDevice));
+      colbert_b_set_ = true;
+    }
     return;
   }
   auto it = targets_.find(name);
@@ -338,8 +373,15 @@ void Encoder::ensure_ws(int64_t tokens, int B) {
 
 void Encoder::forward_dev(const int32_t* ids, const int32_t* mask, const int32_t* types, int B,
                           int S, int mode, int pool, void* out, int out_dtype, int ld_out,
-                          hipStream_t s, const SparseOut* sparse) {
+                          hipStream_t s, const TokenHeads* heads) {
   SR_CHECK(B >= 0 && S >= 1, "encoder: bad batch shape");
+  const SparseOut* sparse = heads ? heads->sparse : nullptr;
+  const MultiVecOut* mv = heads ? heads->multivec : nullptr;
+  SR_CHECK(!heads || sparse || mv, "encoder: an empty token-heads request");
+  if (mv) {
+    SR_CHECK(mode == 0, "encoder: the multi-vector head belongs to the embedding forward");
+    SR_CHECK(B == 0 || (mv->vecs && mv->len), "encoder: null multi-vector output");
+  }
   if (sparse) {
     SR_CHECK(mode == 0, "encoder: the sparse head belongs to the embedding forward");
     sparse_terms_check_args(B, S, sparse->n_special);
@@ -357,6 +399,10 @@ void Encoder::forward_dev(const int32_t* ids, const int32_t* mask, const int32_t
   if (sparse && !(sparse_w_set_ && sparse_b_set_))
     throw Error(SR_ERR_STATE, std::string("encoder: weight not set: sparse_linear.") +
                                   (sparse_w_set_ ? "bias" : "weight"));
+  if (mv && !(colbert_w_set_ && colbert_b_set_))
+    throw Error(SR_ERR_STATE, std::string("encoder: weight not set: colbert_linear.") +
+                                  (colbert_w_set_ ? "bias" : "weight"));
+  if (mv) colbert_pack_check_args(B, S, colbert_dc_);
   if (B == 0) return;
   DeviceGuard g(device_);
   // s == nullptr is the HIP null stream (torch's default stream): use it as-is.
@@ -374,6 +420,11 @@ void Encoder::forward_dev(const int32_t* ids, const int32_t* mask, const int32_t
     sparse_tw_.reserve((size_t)B * S * sizeof(float));
     tok_weight = sparse_tw_.as<float>();
   }
+  if (mv) {  // the head's GEMM output of one launch chunk
+    const size_t need = (size_t)chunk_tokens * colbert_dc_ * sizeof(half_t);
+    if (colbert_v_.bytes < need) SR_HIP(hipEventSynchronize(done_));
+    colbert_v_.reserve(need);
+  }
   half_t* h16 = h16_.as<half_t>();
   float* h32 = h32_.as<float>();
   half_t* qkv = qkv_.as<half_t>();
@@ -388,8 +439,8 @@ void Encoder::forward_dev(const int32_t* ids, const int32_t* mask, const int32_t
   // Only the first token's final state is consumed (CLS pooling / classification head): the last
   // layer runs attention for query row 0 only and its O-projection, LayerNorms and FFN on the
   // B CLS rows (exact: every other row of the last layer is dead).
-  // The sparse head reads every token's final state: its request keeps the full last layer.
-  const bool cls_only = !sparse && ((mode == 1) || (pool == SR_POOL_CLS));
+  // The token heads read every token's final state: their request keeps the full last layer.
+  const bool cls_only = !heads && ((mode == 1) || (pool == SR_POOL_CLS));
 
   const bool fold = fold_enabled();
   if (fold) prepare_fold(s);
@@ -590,6 +641,13 @@ void Encoder::forward_dev(const int32_t* ids, const int32_t* mask, const int32_t
         launch_sparse_terms(cids, cmask, tw, nb, S, sparse->special_ids, sparse->n_special,
                             sparse->terms + b0 * S, sparse->weights + b0 * S, sparse->count + b0, s);
       }
+      if (mv) {  // v = W h + b for every token of the chunk (fp16), then normalise and compact
+        const int dc = colbert_dc_;
+        half_t* v = colbert_v_.as<half_t>();
+        launch_gemm(EPI_BIAS_F16, h16, d, colbert_w_.as<half_t>(), colbert_b_.as<float>(), nullptr, 0, v,
+                    dc, M, dc, d, s);
+        launch_colbert_pack(v, cmask, nb, S, dc, mv->vecs + b0 * S * dc, mv->len + b0, s);
+      }
     } else {
       float* t = clst_.as<float>();
       launch_gemm(EPI_BIAS_TANH_F32, h16, (int64_t)Sf * d, wc_.as<half_t>(), bc_.as<float>(),
@@ -647,13 +705,71 @@ void Encoder::forward_sparse_host(const int32_t* ids, const int32_t* mask, const
   SR_HIP(hipMemcpyAsync(dmask, mask, n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
   if (types) SR_HIP(hipMemcpyAsync(dtypes, types, n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
   const SparseOut so{special_ids, n_special, dtw, dterms, dw, dcount};
-  forward_dev(dids, dmask, dtypes, B, S, 0, pool, dout, SR_DTYPE_F32, cfg_.hidden, stream_, &so);
+  TokenHeads th;
+  th.sparse = &so;
+  forward_dev(dids, dmask, dtypes, B, S, 0, pool, dout, SR_DTYPE_F32, cfg_.hidden, stream_, &th);
   SR_HIP(hipMemcpyAsync(out_dense, dout, (size_t)B * cfg_.hidden * sizeof(float), hipMemcpyDeviceToHost, stream_));
   if (out_tok_weight) SR_HIP(hipMemcpyAsync(out_tok_weight, dtw, n * sizeof(float), hipMemcpyDeviceToHost, stream_));
   SR_HIP(hipMemcpyAsync(out_terms, dterms, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
   SR_HIP(hipMemcpyAsync(out_weights, dw, n * sizeof(float), hipMemcpyDeviceToHost, stream_));
   SR_HIP(hipMemcpyAsync(out_count, dcount, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
   SR_HIP(hipStreamSynchronize(stream_));
+}
+
+void Encoder::forward_multivec_host(const int32_t* ids, const int32_t* mask, const int32_t* types,
+                                    int B, int S, int pool, float* out_dense, float* out_vecs,
+                                    int32_t* out_len, const int32_t* special_ids, int n_special,
+                                    float* out_tok_weight, int32_t* out_terms, float* out_weights,
+                                    int32_t* out_count) {
+  SR_CHECK(B >= 0 && S >= 1, "encoder: bad batch shape");
+  const bool any_sparse = out_tok_weight || out_terms || out_weights || out_count;
+  const bool with_sparse = out_terms && out_weights && out_count;
+  SR_CHECK(!any_sparse || with_sparse,
+           "encoder: the sparse outputs are one group: terms, weights and count together or none");
+  SR_CHECK(B == 0 || (ids && mask && out_dense && out_vecs && out_len), "encoder: null buffer");
+  if (with_sparse) sparse_terms_check_args(B, S, n_special);
+  if (!(colbert_w_set_ && colbert_b_set_))
+    throw Error(SR_ERR_STATE, std::string("encoder: weight not set: colbert_linear.") +
+                                  (colbert_w_set_ ? "bias" : "weight"));
+  colbert_pack_check_args(B, S, colbert_dc_);
+  if (B == 0) return;
+  DeviceGuard g(device_);
+  const size_t n = (size_t)B * S, nv = n * colbert_dc_;
+  int32_t *dids, *dmask, *dtypes = nullptr, *dlen, *dterms = nullptr, *dcount = nullptr;
+  float *dout, *dtw = nullptr, *dw = nullptr;
+  half_t* dvecs;
+  Carve c;
+  c.part(n, &dids, &dmask);
+  if (types) c.part(n, &dtypes);
+  c.part((size_t)B * cfg_.hidden, &dout);
+  c.part(nv, &dvecs);
+  c.part((size_t)B, &dlen);
+  if (with_sparse) {
+    c.part(n, &dtw, &dterms, &dw);
+    c.part((size_t)B, &dcount);
+  }
+  hostio_.carve(c);
+  SR_HIP(hipMemcpyAsync(dids, ids, n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+  SR_HIP(hipMemcpyAsync(dmask, mask, n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+  if (types) SR_HIP(hipMemcpyAsync(dtypes, types, n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+  const SparseOut so{special_ids, n_special, dtw, dterms, dw, dcount};
+  const MultiVecOut mo{dvecs, dlen};
+  TokenHeads th;
+  th.sparse = with_sparse ? &so : nullptr;
+  th.multivec = &mo;
+  forward_dev(dids, dmask, dtypes, B, S, 0, pool, dout, SR_DTYPE_F32, cfg_.hidden, stream_, &th);
+  std::vector<half_t> hv(nv);
+  SR_HIP(hipMemcpyAsync(out_dense, dout, (size_t)B * cfg_.hidden * sizeof(float), hipMemcpyDeviceToHost, stream_));
+  SR_HIP(hipMemcpyAsync(hv.data(), dvecs, nv * sizeof(half_t), hipMemcpyDeviceToHost, stream_));
+  SR_HIP(hipMemcpyAsync(out_len, dlen, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+  if (with_sparse) {
+    if (out_tok_weight) SR_HIP(hipMemcpyAsync(out_tok_weight, dtw, n * sizeof(float), hipMemcpyDeviceToHost, stream_));
+    SR_HIP(hipMemcpyAsync(out_terms, dterms, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+    SR_HIP(hipMemcpyAsync(out_weights, dw, n * sizeof(float), hipMemcpyDeviceToHost, stream_));
+    SR_HIP(hipMemcpyAsync(out_count, dcount, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+  }
+  SR_HIP(hipStreamSynchronize(stream_));
+  for (size_t i = 0; i < nv; ++i) out_vecs[i] = (float)hv[i];
 }
 
 }  // namespace sr

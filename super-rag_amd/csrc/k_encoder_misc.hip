@@ -1123,3 +1123,108 @@ void launch_sparse_terms(const int32_t* ids, const int32_t* mask, const float* t
 }
 
 }  // namespace sr
+
+// ---- multi-vector head (ColBERT / bge-m3 multi-vector; DESIGN.md "Multi-vector retrieval") ----------
+// After the head's GEMM (v = W h + b, fp16, every token of the chunk): u = v / max(||v||, 1e-12) for
+// the positions s >= 1 with mask != 0, compacted in position order; the rows behind them are zero.
+namespace sr {
+
+namespace {
+
+constexpr int CBP_MAX_S = 8192;                // the slot of every position: 32 KiB of LDS
+constexpr int CBP_MAX_THREADS = 1024;
+constexpr int CBP_PER_THREAD = CBP_MAX_S / CBP_MAX_THREADS;
+
+// One workgroup per sequence.  (1) Every thread owns a contiguous run of positions; a block scan of
+// the kept ones (as sparse_terms compacts) gives each its destination row, kept in LDS.  (2) One wave
+// per kept position: 16-byte loads of its dc <= 1024 values (<= 2 per lane), the squared norm in fp32
+// by a wave reduction, 16-byte stores of the scaled row.  (3) Zero rows behind the kept ones and the
+// count.  No atomics.
+__global__ __launch_bounds__(CBP_MAX_THREADS) void colbert_pack_kernel(
+    const half_t* __restrict__ v, const int32_t* __restrict__ mask, int S, int dc,
+    half_t* __restrict__ out, int32_t* __restrict__ out_len) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char colbert_smem[];
+  __shared__ int s_wave[CBP_MAX_THREADS / 64];
+  int* slot = reinterpret_cast<int*>(colbert_smem);          // [S] destination row or -1
+  const int b = blockIdx.x, tid = threadIdx.x, nthr = blockDim.x, lane = tid & 63;
+  const int wave = tid >> 6, nw = nthr >> 6;
+  const int64_t base = (int64_t)b * S;
+  const int C = (S + nthr - 1) / nthr;                       // <= CBP_PER_THREAD (launcher)
+  const int p0 = tid * C;
+  unsigned keep = 0u;
+  int nmine = 0;
+#pragma unroll
+  for (int c = 0; c < CBP_PER_THREAD; ++c) {
+    const int p = p0 + c;
+    if (c < C && p < S && p >= 1 && mask[base + p] != 0) {
+      keep |= 1u << c;
+      ++nmine;
+    }
+  }
+  int len;
+  int q = block_excl_scan(nmine, s_wave, &len);
+#pragma unroll
+  for (int c = 0; c < CBP_PER_THREAD; ++c) {
+    const int p = p0 + c;
+    if (c < C && p < S) slot[p] = (keep & (1u << c)) ? q++ : -1;
+  }
+  __syncthreads();
+  const int nch = dc >> 3;                                   // 16-byte chunks per row, <= 128
+  for (int p = wave; p < S; p += nw) {
+    const int dst = slot[p];
+    if (dst < 0) continue;                                   // (wave-uniform)
+    const half8* src = reinterpret_cast<const half8*>(v + (base + p) * dc);
+    half8 x[2];
+    float ss = 0.f;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int ch = lane + 64 * i;
+      x[i] = half8{0, 0, 0, 0, 0, 0, 0, 0};
+      if (ch < nch) {
+        x[i] = src[ch];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) ss = fmaf((float)x[i][e], (float)x[i][e], ss);
+      }
+    }
+    ss = wave_sum(ss);
+    const float inv = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
+    half8* d = reinterpret_cast<half8*>(out + (base + dst) * dc);
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int ch = lane + 64 * i;
+      if (ch < nch) {
+        half8 y;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) y[e] = (half_t)((float)x[i][e] * inv);
+        d[ch] = y;
+      }
+    }
+  }
+  half8* tail = reinterpret_cast<half8*>(out + (base + len) * dc);
+  const int64_t ntail = (int64_t)(S - len) * nch;
+  const half8 z = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int64_t i = tid; i < ntail; i += nthr) tail[i] = z;
+  if (tid == 0) out_len[b] = len;
+}
+
+}  // namespace
+
+void colbert_pack_check_args(int B, int S, int dc) {
+  SR_CHECK(B >= 0, "colbert_pack: negative batch");
+  SR_CHECK(S >= 1 && S <= CBP_MAX_S, "colbert_pack: S must be in [1, 8192]");
+  SR_CHECK(dc >= 128 && dc <= 1024 && dc % 128 == 0, "colbert_pack: dc must be a multiple of 128, <= 1024");
+}
+
+void launch_colbert_pack(const half_t* v, const int32_t* mask, int B, int S, int dc, half_t* out,
+                         int32_t* out_len, hipStream_t s) {
+  colbert_pack_check_args(B, S, dc);
+  if (B == 0) return;
+  const int threads = (int)std::min<int64_t>(CBP_MAX_THREADS, round_up(S, 64));
+  const size_t smem = (size_t)S * sizeof(int);
+  // the GEMM output in, the packed rows out, the mask and the count
+  ProfScope prof("colbert_pack", s, 3.0 * B * S * dc, (double)B * (S * (dc * 4.0 + 4.0) + 4.0));
+  hipLaunchKernelGGL(colbert_pack_kernel, dim3(B), dim3(threads), smem, s, v, mask, S, dc, out, out_len);
+  SR_LAUNCH_CHECK();
+}
+
+}  // namespace sr

@@ -149,6 +149,12 @@ void sparse_terms_check_args(int B, int S, int n_special);
 void launch_sparse_terms(const int32_t* ids, const int32_t* mask, const float* tw, int B, int S,
                          const int32_t* special_ids, int n_special, int32_t* out_terms,
                          float* out_weights, int32_t* out_count, hipStream_t s);
+// multi-vector head (k_encoder_misc.hip colbert_pack): v [B][S][dc] fp16 (the head's GEMM output) ->
+// out [B][S][dc]: the rows of the positions s >= 1 with mask != 0, L2-normalised in fp32
+// (v / max(||v||, 1e-12)) and compacted in position order, zero rows behind them; out_len [B]
+void colbert_pack_check_args(int B, int S, int dc);
+void launch_colbert_pack(const half_t* v, const int32_t* mask, int B, int S, int dc, half_t* out,
+                         int32_t* out_len, hipStream_t s);
 void launch_cls_logits(const float* t, const float* w, const float* bias, int P, int d,
                        int labels, float* out, hipStream_t s);
 void launch_normalize_rows(const void* x, int dtype, int64_t n, int dim, half_t* out, int ld,
@@ -271,6 +277,19 @@ void launch_score_fuse(const float* score_a, const int64_t* rows_a, int ka, cons
 void launch_score_rows(const half_t* corpus, int ld, int64_t n_rows, const uint8_t* live,
                        const half_t* qn, const int64_t* rows, int B, int K, int64_t row_offset,
                        float* out, hipStream_t s);
+
+// k_multivec.hip — MaxSim of (query, row) pairs over a multi-vector token pool (the function is
+// stated in include/super_rag_mi355x.h): pool [n_tokens][dim] fp16, off [n_rows + 1], live [n_rows];
+// q [B][ld_q][dim] fp16, q_len [B] (clamped to ld_q and 512), rows [B][K]; out [B][K], -inf for a row outside
+// [0, n_rows), dead or empty and for an empty query.  tokens_hint: candidate tokens, profiling only.
+// maxsim_check_args throws SR_ERR_INVALID outside the limits.  launch_mv_pack copies row i of src
+// [n][ld_tok][dim] (off[i + 1] - off[i] tokens) to pool + off[i] * dim.
+void maxsim_check_args(int dim, int B, int ld_q, int K);
+void launch_maxsim(const half_t* pool, const int64_t* off, const uint8_t* live, int64_t n_rows,
+                   int dim, const half_t* q, const int32_t* q_len, int B, int ld_q,
+                   const int64_t* rows, int K, float* out, double tokens_hint, hipStream_t s);
+void launch_mv_pack(const half_t* src, const int64_t* off, int64_t n, int ld_tok, int dim,
+                    half_t* pool, hipStream_t s);
 
 // k_lex.hip — reciprocal-rank fusion of two ranked row lists per query (-1 padded), fp64 scores.
 void launch_rrf_fuse(const int64_t* rows_a, int ka, const int64_t* rows_b, int kb, int B,

@@ -235,10 +235,27 @@ class Encoder {
     float* weights;               // B x S device
     int32_t* count;               // B device
   };
+  // the multi-vector (ColBERT) head's outputs: the compacted unit token vectors and their count
+  struct MultiVecOut {
+    half_t* vecs;                 // B x S x dc device; rows [len, S) of a sequence are zero
+    int32_t* len;                 // B device
+  };
+  // one request for the heads that read every token's final state: either or both
+  struct TokenHeads {
+    const SparseOut* sparse = nullptr;
+    const MultiVecOut* multivec = nullptr;
+  };
   // mode 0: pooled embeddings to `out` (dtype/ld_out); mode 1: classifier logits (fp32).
   void forward_dev(const int32_t* ids, const int32_t* mask, const int32_t* types, int B, int S,
                    int mode, int pool, void* out, int out_dtype, int ld_out, hipStream_t s,
-                   const SparseOut* sparse = nullptr);
+                   const TokenHeads* heads = nullptr);
+  // host buffers, blocking: the dense embedding, the multi-vector (fp16 values as fp32, B x S x dc)
+  // and, with out_terms set, the sparse outputs of forward_sparse_host
+  void forward_multivec_host(const int32_t* ids, const int32_t* mask, const int32_t* types, int B, int S,
+                             int pool, float* out_dense, float* out_vecs, int32_t* out_len,
+                             const int32_t* special_ids, int n_special, float* out_tok_weight,
+                             int32_t* out_terms, float* out_weights, int32_t* out_count);
+  int colbert_dim() const { return colbert_w_set_ ? colbert_dc_ : 0; }
   // host buffers, blocking: the dense embedding (fp32 B x hidden) and the sparse outputs
   void forward_sparse_host(const int32_t* ids, const int32_t* mask, const int32_t* types, int B, int S,
                            int pool, float* out_dense, const int32_t* special_ids, int n_special,
@@ -297,6 +314,11 @@ class Encoder {
   // token weights of one call when the caller wants none
   DevBuf sparse_w_, sparse_b_, sparse_tw_;
   bool sparse_w_set_ = false, sparse_b_set_ = false;
+  // multi-vector head (optional: "colbert_linear.weight" [dc, hidden] fp16 in the GEMM's W layout,
+  // "colbert_linear.bias" [dc] fp32) and the GEMM output of one launch chunk
+  DevBuf colbert_w_, colbert_b_, colbert_v_;
+  bool colbert_w_set_ = false, colbert_b_set_ = false;
+  int colbert_dc_ = 0;
   DevBuf statA_, statB_, mrA_, mrB_;  // per-row LayerNorm partials / (mu, rstd) (folded path)
   bool fold_ready_ = false;  // folded weights match the current weights
   int fp8_ = 0;
@@ -419,6 +441,49 @@ class LexIndex {
   std::vector<uint8_t> live_host_;
   std::vector<int64_t> off_host_;
   int64_t version_ = 0, mask_key_ = 0, mask_version_ = -1;
+};
+
+// ------------------------------------------------------------------------------------------------
+// Multi-vector index over the rows of a store (multivec.hip, k_multivec.hip): one fp16 token pool
+// [n_tokens][dim] in HBM, the first token of every row (int64) and live flags; scores are MaxSim.
+class MultiVecIndex {
+ public:
+  MultiVecIndex(int dim, int device);
+  ~MultiVecIndex();
+
+  int dim() const { return dim_; }
+  int device() const { return device_; }
+  // n rows: row i is the tokens vecs[off[i] .. off[i+1]) (fp32 host, rounded to fp16)
+  void add_host(const int64_t* off, const float* vecs, int64_t n, int64_t* first_row);
+  // n rows: row i is the first len[i] tokens of vecs[i] ([n][ld_tok][dim] fp16 device, len device);
+  // reads the lengths back (synchronises s)
+  void add_dev(const half_t* vecs, const int32_t* len, int64_t n, int ld_tok, int64_t* first_row,
+               hipStream_t s);
+  void remove(const int64_t* rows, int64_t n);
+  void stats(int64_t* n_rows, int64_t* n_live, int64_t* n_tokens) const;
+  void get(int64_t row, float* out, int64_t cap, int64_t* n_tok);
+  void score_rows_dev(const half_t* q, const int32_t* q_len, int B, int ld_q, const int64_t* rows,
+                      int K, float* out, hipStream_t s);
+  void score_rows_host(const float* q, const int32_t* q_len, int B, int ld_q, const int64_t* rows,
+                       int K, float* out);
+
+  std::mutex mu;
+
+ private:
+  void begin(hipStream_t s) { SR_HIP(hipStreamWaitEvent(s, done_, 0)); }
+  void end(hipStream_t s) { SR_HIP(hipEventRecord(done_, s)); }
+  // room for the rows and tokens of an append (doubling; the contents move on stream s)
+  void ensure_capacity(int64_t rows, int64_t tokens, hipStream_t s);
+  // after the tokens are in the pool: offsets, live flags and the counts of n new rows
+  void commit(const std::vector<int64_t>& len, hipStream_t s);
+
+  int dim_, device_;
+  hipStream_t stream_ = nullptr;
+  hipEvent_t done_ = nullptr;
+  int64_t n_rows_ = 0, n_live_ = 0, n_tokens_ = 0, cap_rows_ = 0, cap_tokens_ = 0;
+  DevBuf pool_, off_, live_, hostio_;
+  std::vector<int64_t> off_host_{0};   // n_rows_ + 1 entries
+  std::vector<uint8_t> live_host_;
 };
 
 }  // namespace sr

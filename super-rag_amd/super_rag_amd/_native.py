@@ -38,6 +38,7 @@ SR_FUSE_FLOOR_FULL = 2
 SR_LEX_BM25 = 0
 SR_LEX_IMPACT = 1
 SR_IMPACT_MAX_WEIGHT = 16.0
+SR_MV_MAX_QUERY_TOKENS = 512
 
 
 class NativeUnavailableError(RuntimeError):
@@ -195,6 +196,23 @@ SIGNATURES = {
     "sr_encoder_forward_sparse": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
                                           c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                           c_void_p]),
+    "sr_encoder_colbert_dim": (c_int, [c_void_p, P_I32]),
+    "sr_encoder_forward_multivec_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                                c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "sr_encoder_forward_multivec": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int,
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
+                                            c_void_p, c_void_p, c_void_p]),
+    "sr_mv_create": (c_int, [c_int, c_int, POINTER(c_void_p)]),
+    "sr_mv_add": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, P_I64]),
+    "sr_mv_add_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, P_I64, c_void_p]),
+    "sr_mv_remove": (c_int, [c_void_p, c_void_p, c_int64]),
+    "sr_mv_stats": (c_int, [c_void_p, P_I64, P_I64, P_I64]),
+    "sr_mv_get": (c_int, [c_void_p, c_int64, c_void_p, c_int64, P_I64]),
+    "sr_mv_score_rows_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p,
+                                     c_void_p]),
+    "sr_mv_score_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "sr_mv_destroy": (None, [c_void_p]),
     "sr_score_fuse_sides": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
                                     c_void_p, c_int, c_int, c_float, c_float, c_float, c_float, c_int,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_int]),

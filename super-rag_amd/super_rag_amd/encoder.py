@@ -322,17 +322,42 @@ def load_sparse_head(directory: str | None, hidden: int):
     return w.astype(np.float32), b.astype(np.float32)
 
 
+def load_colbert_head(directory: str | None, hidden: int):
+    """bge-m3's ``colbert_linear.pt`` of a model directory (a torch state dict: weight [dc, hidden],
+    bias [dc]) -> (weight [dc, hidden] fp32, bias [dc] fp32), or None when the directory has none.
+    dc must be a multiple of 128, at most 1024 (the head runs on the encoder's GEMM)."""
+    if not directory:
+        return None
+    path = os.path.join(directory, "colbert_linear.pt")
+    if not os.path.exists(path):
+        return None
+    import torch
+    sd = torch.load(path, map_location="cpu", weights_only=True)
+    try:
+        w = sd["weight"].float().numpy()
+        b = sd["bias"].float().numpy().reshape(-1)
+    except (KeyError, TypeError, AttributeError) as e:
+        raise ModelAssetsError(f"{path}: not a colbert_linear state dict (weight, bias)") from e
+    if w.ndim != 2 or w.shape[1] != hidden or b.size != w.shape[0]:
+        raise ModelAssetsError(f"{path}: weight is {tuple(w.shape)} and bias has {b.size} values, "
+                               f"expected [dc, {hidden}] and dc")
+    if w.shape[0] % 128 or not 0 < w.shape[0] <= 1024:
+        raise ModelAssetsError(f"{path}: dc = {w.shape[0]} must be a multiple of 128, at most 1024")
+    return np.ascontiguousarray(w, dtype=np.float32), b.astype(np.float32)
+
+
 class Encoder:
     """One encoder instance resident on one device (sr_encoder_* in the C-ABI)."""
 
     def __init__(self, spec: ModelSpec, device: int = 0, weights: dict | None = None,
                  seed: int = 0, max_tokens: int = 0, init_style: str = "hf",
                  checkpoint: str | None = None):
-        sparse = None
+        sparse = colbert = None
         if weights is None:   # resolve first: a missing checkpoint fails before any device work
             weights = model_weights(spec, checkpoint, seed, init_style)
-            sparse = load_sparse_head(os.path.dirname(checkpoint) if checkpoint else spec.asset_dir,
-                                      spec.hidden)
+            head_dir = os.path.dirname(checkpoint) if checkpoint else spec.asset_dir
+            sparse = load_sparse_head(head_dir, spec.hidden)
+            colbert = load_colbert_head(head_dir, spec.hidden)
         N.require_gpu()
         self.spec = spec
         self.device = int(device)
@@ -347,6 +372,9 @@ class Encoder:
         self.has_sparse_head = False
         if sparse is not None:
             self.set_sparse_head(*sparse)
+        self.has_colbert_head = False
+        if colbert is not None:
+            self.set_colbert_head(*colbert)
 
     def load_weights(self, weights: dict) -> None:
         for name, v in weights.items():
@@ -368,6 +396,27 @@ class Encoder:
         N.call("sr_encoder_set_weight", self._h, b"sparse_linear.weight", N.ptr(w), w.size)
         N.call("sr_encoder_set_weight", self._h, b"sparse_linear.bias", N.ptr(b), b.size)
         self.has_sparse_head = True
+
+    def set_colbert_head(self, weight, bias) -> None:
+        """bge-m3's colbert_linear: weight [dc, hidden] and bias [dc], dc a multiple of 128 and at
+        most 1024; kept fp16 / fp32 on the device.  Optional: without it only embed_multivec* fail."""
+        w = np.ascontiguousarray(np.asarray(weight, dtype=np.float32))
+        b = np.ascontiguousarray(np.asarray(bias, dtype=np.float32).reshape(-1))
+        if w.ndim != 2 or w.shape[1] != self.spec.hidden or b.size != w.shape[0]:
+            raise ValueError(f"multi-vector head needs weight [dc, {self.spec.hidden}] and bias [dc], got "
+                             f"{w.shape} and {b.size} values")
+        if w.shape[0] % 128 or not 0 < w.shape[0] <= 1024:
+            raise ValueError(f"multi-vector head: dc = {w.shape[0]} must be a multiple of 128, at most 1024")
+        N.call("sr_encoder_set_weight", self._h, b"colbert_linear.weight", N.ptr(w), w.size)
+        N.call("sr_encoder_set_weight", self._h, b"colbert_linear.bias", N.ptr(b), b.size)
+        self.has_colbert_head = True
+
+    @property
+    def colbert_dim(self) -> int:
+        """dc of the multi-vector head, 0 without one (sr_encoder_colbert_dim)."""
+        n = ctypes.c_int32(0)
+        N.call("sr_encoder_colbert_dim", self._h, ctypes.byref(n))
+        return int(n.value)
 
     def set_fp8(self, mode: int) -> None:
         """Opt-in fp8 precision mode (LN-folded fp16-residual encoders, e.g. cross-encoders):
@@ -427,6 +476,66 @@ class Encoder:
                N.ptr(count))
         sparse = [(terms[b, :count[b]].copy(), weights[b, :count[b]].copy()) for b in range(B)]
         return (dense, sparse, tw) if return_token_weights else (dense, sparse)
+
+    def embed_multivec(self, ids, mask, type_ids=None, pool: str | None = None,
+                       with_sparse: bool = False, special_ids=None):
+        """One forward pass -> (dense [B, hidden] fp32, [vecs_b fp32 [len_b, dc]] per sequence
+        [, the sparse list of embed_sparse]): the dense embedding of embed() and bge-m3's
+        multi-vector, the unit vector of every valid token but the first (CLS / <s>), in position
+        order (the fp16 values the device keeps).  sr_encoder_forward_multivec; needs
+        set_colbert_head (and set_sparse_head for with_sparse)."""
+        ids = np.ascontiguousarray(np.asarray(ids, dtype=np.int32))
+        mask = np.ascontiguousarray(np.asarray(mask, dtype=np.int32))
+        tt = None if type_ids is None else np.ascontiguousarray(np.asarray(type_ids, dtype=np.int32))
+        B, S = ids.shape
+        dc = max(self.colbert_dim, 1)
+        dense = np.empty((B, self.spec.hidden), dtype=np.float32)
+        vecs = np.empty((B, S, dc), dtype=np.float32)
+        lens = np.zeros(B, dtype=np.int32)
+        sp = terms = weights = count = None
+        if with_sparse:
+            sp = self._special(special_ids)
+            terms = np.empty((B, S), dtype=np.int32)
+            weights = np.empty((B, S), dtype=np.float32)
+            count = np.zeros(B, dtype=np.int32)
+        p = N.SR_POOL_CLS if (pool or self.spec.pool) == "cls" else N.SR_POOL_MEAN
+        N.call("sr_encoder_forward_multivec", self._h, N.ptr(ids), N.ptr(mask), N.ptr(tt), B, S, p,
+               N.ptr(dense), N.ptr(vecs), N.ptr(lens), N.ptr(sp), int(sp.size) if with_sparse else 0,
+               None, N.ptr(terms), N.ptr(weights), N.ptr(count))
+        mv = [vecs[b, :lens[b]].copy() for b in range(B)]
+        if not with_sparse:
+            return dense, mv
+        sparse = [(terms[b, :count[b]].copy(), weights[b, :count[b]].copy()) for b in range(B)]
+        return dense, mv, sparse
+
+    def embed_multivec_dev(self, ids, mask, type_ids=None, out=None, ld_out: int | None = None,
+                           fp16: bool = True, pool: str | None = None, with_sparse: bool = False,
+                           special_ids=None, stream=None):
+        """embed_multivec on device tensors (sr_encoder_forward_multivec_dev), asynchronous on
+        ``stream`` -> (dense as embed_dev, vecs fp16 [B, S, dc] with the rows past the length zero,
+        lens int32 [B] [, terms, weights, count as embed_sparse_dev]): vecs and lens are what
+        NativeMultiVectorIndex.add_dev takes."""
+        import torch
+        B, S = ids.shape
+        ld = ld_out or self.spec.hidden
+        if out is None:
+            out = torch.empty((B, ld), dtype=torch.float16 if fp16 else torch.float32,
+                              device=ids.device)
+        dt = N.SR_DTYPE_F16 if out.dtype == torch.float16 else N.SR_DTYPE_F32
+        p = N.SR_POOL_CLS if (pool or self.spec.pool) == "cls" else N.SR_POOL_MEAN
+        vecs = torch.empty((B, S, max(self.colbert_dim, 1)), dtype=torch.float16, device=ids.device)
+        lens = torch.empty((B,), dtype=torch.int32, device=ids.device)
+        sp = terms = weights = count = None
+        if with_sparse:
+            sp = self._special(special_ids)
+            terms = torch.empty((B, S), dtype=torch.int32, device=ids.device)
+            weights = torch.empty((B, S), dtype=torch.float32, device=ids.device)
+            count = torch.empty((B,), dtype=torch.int32, device=ids.device)
+        N.call("sr_encoder_forward_multivec_dev", self._h, N.ptr(ids), N.ptr(mask), N.ptr(type_ids), B, S,
+               p, N.ptr(out), dt, out.shape[1], N.ptr(vecs), N.ptr(lens), N.ptr(sp),
+               int(sp.size) if with_sparse else 0, None, N.ptr(terms), N.ptr(weights), N.ptr(count),
+               N.stream_handle(stream))
+        return (out, vecs, lens, terms, weights, count) if with_sparse else (out, vecs, lens)
 
     def _special(self, special_ids) -> np.ndarray:
         if special_ids is None:
