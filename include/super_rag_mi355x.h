@@ -427,19 +427,40 @@ int sr_lex_score_rows_weighted(sr_lex* x, const int64_t* qoff, const int32_t* qt
  *                   int32 [n], device: what sr_encoder_forward_multivec_dev writes).  Reads the lengths
  *                   back to size the pool: synchronises `stream`, and has finished when it returns.
  *   sr_mv_remove    tombstones rows (in range; twice is harmless); the tokens stay in the pool.
- *   sr_mv_get       row's tokens as fp32 (the stored fp16 values) into out (room for cap tokens; at
+ *   sr_mv_get       row's tokens as fp32 (the stored values) into out (room for cap tokens; at
  *                   most cap are written); n_tok receives the row's count.
  *   sr_mv_score_rows_dev  q fp16 [B, ld_q, dim], q_len int32 [B], rows int64 [B, K], out_score fp32
  *                   [B, K], all device; the query rows at and past q_len[b] are never read.
  *                   Asynchronous on `stream`.
  *   sr_mv_score_rows      the same on host buffers, q fp32 rounded to nearest fp16.  Blocking.
- * Not provided: snapshots and compaction, a multi-device variant, a whole-corpus MaxSim scan, fp8
- * token vectors, a fused rerank entry point (multivec.m3_rerank composes the existing ones).
+ *   sr_mv_create_dtype    sr_mv_create with the pool's dtype: SR_DTYPE_F16 (what sr_mv_create means) or
+ *                   SR_DTYPE_FP8_E4M3; anything else is SR_ERR_INVALID before any device work.
+ *   sr_mv_info      the pool's dtype and pool_bytes = n_tokens * dim * element size (2 or 1): the
+ *                   stored tokens, not the capacity.  Either output may be NULL.
+ * fp8 pool (SR_DTYPE_FP8_E4M3, opt-in; meant for unit-norm tokens, which is what the head emits): a
+ * token element x is stored as the one byte e4m3_rne(256 * fp16(x)): OCP e4m3fn, round to nearest
+ * even, saturating at +-448 (the dense store's fp8 scan format).  No per-token scale, no fp16 copy; a
+ * pool row is dim bytes.  An element with |x| > 1.75 saturates (to +-1.75), on both add paths.  The
+ * dequantised value of a byte c is d^ = e4m3_value(c) / 256, exact in fp32; for a unit token
+ * ||d^ - d|| <= 2^-4 ||d|| + sqrt(dim) 2^-18.  sr_mv_add rounds fp32 -> fp16 as on an fp16 pool and
+ * then quantises with sr_mv_add_dev's kernel (the double rounding is the definition), so both adds of
+ * the same values store the same bytes; sr_mv_get returns d^.  Score contract:
+ *   maxsim8(q, row) = (1 / Lq) sum_i max_j (q_i . d^_j)
+ * with the caller's fp16 query, unquantised, and fp32 accumulation: the fp16 definition applied to
+ * the dequantised tokens, under the same bound |score - exact| <= (dim + Lq) 2^-23 max||q_i||
+ * max||d^_j|| and the same bit-identity and -inf rules.  Quantisation changes what is stored, never how
+ * it is scored.  Everything else (growth, remove, stats, both score entry points, the limits) is the
+ * same on both dtypes.
+ * Not provided: snapshots and compaction, a multi-device variant, a whole-corpus MaxSim scan,
+ * per-token scales or residual codecs, quantised queries, a fused rerank entry point
+ * (multivec.m3_rerank composes the existing ones).
  * ---------------------------------------------------------------------------------------------- */
 #define SR_MV_MAX_QUERY_TOKENS 512
 typedef struct sr_mv sr_mv;
 
 int sr_mv_create(int dim, int device, sr_mv** out);
+int sr_mv_create_dtype(int dim, int device, int dtype, sr_mv** out);
+int sr_mv_info(sr_mv* x, int* dtype, int64_t* pool_bytes);
 int sr_mv_add(sr_mv* x, const int64_t* off, const float* vecs, int64_t n, int64_t* first_row);
 int sr_mv_add_dev(sr_mv* x, const void* vecs, const int32_t* len, int64_t n, int ld_tok,
                   int64_t* first_row, void* stream);

@@ -1249,13 +1249,27 @@ int sr_encoder_forward_multivec(sr_encoder* e, const int32_t* ids, const int32_t
 }
 
 // ---- multi-vector index ----------------------------------------------------------------------
-int sr_mv_create(int dim, int device, sr_mv** out) {
+int sr_mv_create_dtype(int dim, int device, int dtype, sr_mv** out) {
   SR_API_BEGIN
   SR_NONNULL(out);
   *out = nullptr;
   SR_CHECK(dim >= 64 && dim <= 1024 && dim % 64 == 0, "mv: dim must be a multiple of 64, <= 1024");
-  auto* x = new sr_mv{new sr::MultiVecIndex(dim, device)};
+  SR_CHECK(dtype == SR_DTYPE_F16 || dtype == SR_DTYPE_FP8_E4M3,
+           "mv: dtype must be SR_DTYPE_F16 or SR_DTYPE_FP8_E4M3");
+  auto* x = new sr_mv{new sr::MultiVecIndex(dim, device, dtype)};
   *out = x;
+  SR_API_END
+}
+
+int sr_mv_create(int dim, int device, sr_mv** out) {
+  return sr_mv_create_dtype(dim, device, SR_DTYPE_F16, out);
+}
+
+int sr_mv_info(sr_mv* x, int* dtype, int64_t* pool_bytes) {
+  SR_API_BEGIN
+  SR_NONNULL(x);
+  std::lock_guard<std::mutex> lk(x->impl->mu);
+  x->impl->info(dtype, pool_bytes);
   SR_API_END
 }
 

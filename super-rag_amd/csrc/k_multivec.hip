@@ -25,7 +25,23 @@
 // order and the summation tree are fixed, so its bits do not depend on B, K, the grouping or the
 // other candidates.  Queries longer than 64 tokens re-stream the candidates once per 64-token block.
 // LDS: 64 x round_up(dim, 128) x 2 B (128 KiB at dim 1024) + 4.5 KiB of static state.
+//
+// maxsim_kernel<true> is the same kernel over an fp8 pool (SR_DTYPE_FP8_E4M3: a token element x is the
+// byte e4m3(256 fp16(x)), a pool row is dim bytes).  Only the candidate loads, their conversion and
+// the last scale differ:
+//   - a 16-byte load carries 16 columns.  A step is 128 columns: lane group g loads bytes [32 g,
+//     32 g + 32) of the step (two loads), so the four lanes of a token still cover one whole 128-byte
+//     line; the 8 columns of MFMA m (0 .. 3) of the step are chunk 16 ks + 4 g + m of the row, and the
+//     query fragment is read at that chunk.  dim % 128 == 64 ends on a half step of 64 columns: one
+//     load of bytes [16 g, 16 g + 16), chunks 16 ks + 2 g + m, m < 2.  Four steps (8 loads per lane,
+//     the fp16 kernel's bytes in flight, twice its columns) form a group.
+//   - the bytes become MFMA operands in registers by v_cvt_scalef32_pk_f16_fp8 with scale 1: the fp16
+//     value of 256 x, exact (every e4m3 value is a normal fp16: the smallest is 2^-9), eight packed
+//     conversions per load.  The query stays the caller's fp16.
+//   - the factor 2^-8 is applied once, in fp32, to the finished sum (a power of two: exact).
+// Everything else, the fp16 instantiation included, is the code above unchanged.
 #include <algorithm>
+#include <type_traits>
 
 #include "sr_common.h"
 #include "sr_kernels.h"
@@ -39,8 +55,10 @@ constexpr int MV_WAVES = MV_THREADS / 64;
 constexpr int MV_QT = 64;     // query tokens per LDS block
 constexpr int MV_MAXC = 32;   // candidates per workgroup
 
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
 struct MvArgs {
-  const half_t* pool;     // [n_tokens][dim]
+  const void* pool;       // [n_tokens][dim] fp16, or e4m3 bytes (maxsim_kernel<true>)
   const int64_t* off;     // [n_rows + 1] first token of each row
   const uint8_t* live;    // [n_rows]
   int64_t n_rows;
@@ -51,7 +69,18 @@ struct MvArgs {
   int ld_q, dim, K, cpw;
 };
 
+// eight e4m3 bytes -> the fp16 values of the same numbers, in byte order
+__device__ __forceinline__ half8 e4m3x8_to_f16(uint32_t w0, uint32_t w1) {
+  const half2_t a = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)w0, 1.f, false);
+  const half2_t b = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)w0, 1.f, true);
+  const half2_t c = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)w1, 1.f, false);
+  const half2_t d = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8((int)w1, 1.f, true);
+  return half8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
+}
+
+template <bool FP8>
 __global__ __launch_bounds__(MV_THREADS) void maxsim_kernel(MvArgs a) {
+  using Buf = std::conditional_t<FP8, u32x4, half8>;  // one 16-byte load
   extern __shared__ __attribute__((aligned(16))) unsigned char mv_smem[];
   __shared__ int64_t c_off[MV_MAXC];
   __shared__ int c_len[MV_MAXC];
@@ -83,7 +112,8 @@ __global__ __launch_bounds__(MV_THREADS) void maxsim_kernel(MvArgs a) {
   }
   __syncthreads();
 
-  const int nk = dim >> 6, ng = (nk + 3) >> 2, nchunk = dim >> 3;
+  // steps of one token row: 64 columns (fp16) or 128 columns plus, at dim % 128 == 64, a half step
+  const int nfull = dim >> 7, nk = FP8 ? (dim + 127) >> 7 : dim >> 6, ng = (nk + 3) >> 2, nchunk = dim >> 3;
   const int lds_ld = (dim + 127) & ~127;
   const int nqb = (Lq + MV_QT - 1) / MV_QT;
   int epoch = 0;  // candidates reduced so far: picks the red buffer
@@ -108,36 +138,76 @@ __global__ __launch_bounds__(MV_THREADS) void maxsim_kernel(MvArgs a) {
     auto tiles_of = [&](int c) { return (__builtin_amdgcn_readfirstlane(c_len[c]) + 15) >> 4; };
     // 16-byte loads of group g of tile t of candidate c: this lane's token, chunks 2 gl, 2 gl + 1
     // of the (<= 4) 64-column steps of the group
-    auto load = [&](half8 (&buf)[8], int c, int t, int g) {
+    auto load = [&](Buf (&buf)[8], int c, int t, int g) {
       const int len = __builtin_amdgcn_readfirstlane(c_len[c]);
       const int tok = min(t * 16 + r16, len - 1);
-      const half_t* p = a.pool + (c_off[c] + tok) * dim + gl * 16;
+      if constexpr (FP8) {
+        // bytes [32 gl, 32 gl + 32) of every 128-column step, [16 gl, 16 gl + 16) of a last half step
+        const uint8_t* p = static_cast<const uint8_t*>(a.pool) + (c_off[c] + tok) * dim;
 #pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int ks = g * 4 + u;
-        if (ks < nk) {
-          buf[2 * u] = *reinterpret_cast<const half8*>(p + ks * 64);
-          buf[2 * u + 1] = *reinterpret_cast<const half8*>(p + ks * 64 + 8);
+        for (int u = 0; u < 4; ++u) {
+          const int ks = g * 4 + u;
+          const bool full = ks < nfull;
+          if (ks < nk) {
+            buf[2 * u] = *reinterpret_cast<const u32x4*>(p + ks * 128 + gl * (full ? 32 : 16));
+            if (full) buf[2 * u + 1] = *reinterpret_cast<const u32x4*>(p + ks * 128 + gl * 32 + 16);
+          }
+        }
+      } else {
+        const half_t* p = static_cast<const half_t*>(a.pool) + (c_off[c] + tok) * dim + gl * 16;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int ks = g * 4 + u;
+          if (ks < nk) {
+            buf[2 * u] = *reinterpret_cast<const half8*>(p + ks * 64);
+            buf[2 * u + 1] = *reinterpret_cast<const half8*>(p + ks * 64 + 8);
+          }
         }
       }
     };
     float4v acc[4];
 #pragma unroll
     for (int qi = 0; qi < 4; ++qi) acc[qi] = float4v{0.f, 0.f, 0.f, 0.f};
-    auto compute = [&](const half8 (&buf)[8], int g) {
+    // one MFMA k-step: 8 columns per lane, the query fragment at the same chunk of its row
+    auto mfma_chunk = [&](const half8 da, int chunk) {
+      const half_t* f = qtile + r16 * lds_ld + ((chunk ^ r16) << 3);
+#pragma unroll
+      for (int qi = 0; qi < 4; ++qi) {
+        if (qi < nqt) {
+          const half8 fb = *reinterpret_cast<const half8*>(f + qi * 16 * lds_ld);
+          acc[qi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(da, fb, acc[qi], 0, 0, 0);
+        }
+      }
+    };
+    auto compute = [&](const Buf (&buf)[8], int g) {
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int ks = g * 4 + u;
-        if (ks < nk) {
+        if constexpr (FP8) {
+          const bool full = ks < nfull;
+          if (ks < nk) {  // chunks 4 gl .. 4 gl + 3 of a step's 16, 2 gl and 2 gl + 1 of a half step's 8
+            const int chunk = ks * 16 + gl * (full ? 4 : 2);
+            const u32x4 w0 = buf[2 * u];
+            mfma_chunk(e4m3x8_to_f16(w0[0], w0[1]), chunk);
+            mfma_chunk(e4m3x8_to_f16(w0[2], w0[3]), chunk + 1);
+            if (full) {
+              const u32x4 w1 = buf[2 * u + 1];
+              mfma_chunk(e4m3x8_to_f16(w1[0], w1[1]), chunk + 2);
+              mfma_chunk(e4m3x8_to_f16(w1[2], w1[3]), chunk + 3);
+            }
+          }
+        } else {
+          if (ks < nk) {
 #pragma unroll
-          for (int s = 0; s < 2; ++s) {
-            const int chunk = ks * 8 + 2 * gl + s;
-            const half_t* f = qtile + r16 * lds_ld + ((chunk ^ r16) << 3);
+            for (int s = 0; s < 2; ++s) {
+              const int chunk = ks * 8 + 2 * gl + s;
+              const half_t* f = qtile + r16 * lds_ld + ((chunk ^ r16) << 3);
 #pragma unroll
-            for (int qi = 0; qi < 4; ++qi) {
-              if (qi < nqt) {
-                const half8 fb = *reinterpret_cast<const half8*>(f + qi * 16 * lds_ld);
-                acc[qi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(buf[2 * u + s], fb, acc[qi], 0, 0, 0);
+              for (int qi = 0; qi < 4; ++qi) {
+                if (qi < nqt) {
+                  const half8 fb = *reinterpret_cast<const half8*>(f + qi * 16 * lds_ld);
+                  acc[qi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(buf[2 * u + s], fb, acc[qi], 0, 0, 0);
+                }
               }
             }
           }
@@ -151,7 +221,7 @@ __global__ __launch_bounds__(MV_THREADS) void maxsim_kernel(MvArgs a) {
       ++nc;
       nt = wave;
     }
-    half8 bufA[8], bufB[8];
+    Buf bufA[8], bufB[8];
     int par = 0;
     if (nc < C) load(bufA, nc, nt, ngi);
 
@@ -208,7 +278,11 @@ __global__ __launch_bounds__(MV_THREADS) void maxsim_kernel(MvArgs a) {
         if (lane == 0) {
           const float tot = (qb ? psum[c] : 0.f) + s;
           psum[c] = tot;
-          if (qb == nqb - 1) a.out[ob + c] = len > 0 ? tot / (float)Lq : -INFINITY;
+          if constexpr (FP8) {  // the operands were 256 d; 2^-8 is exact
+            if (qb == nqb - 1) a.out[ob + c] = len > 0 ? tot / (float)Lq * 0.00390625f : -INFINITY;
+          } else {
+            if (qb == nqb - 1) a.out[ob + c] = len > 0 ? tot / (float)Lq : -INFINITY;
+          }
         }
       }
     }
@@ -228,6 +302,25 @@ __global__ __launch_bounds__(256) void mv_pack_kernel(const half_t* __restrict__
     d[p] = s[p];
 }
 
+// the same into an fp8 pool: 16 fp16 values (two 16-byte loads) -> 16 bytes e4m3(256 x), one 16-byte
+// store.  |x| > 1.75 saturates at +-448 (e4m3x4 clamps).
+__global__ __launch_bounds__(256) void mv_pack_fp8_kernel(const half_t* __restrict__ src,
+                                                          const int64_t* __restrict__ off, int64_t ld_tok,
+                                                          int dim, uint8_t* __restrict__ pool) {
+  const int64_t i = blockIdx.x;
+  const int64_t o = off[i];
+  const int64_t nch = (off[i + 1] - o) * (int64_t)(dim >> 4);
+  const half8* s = reinterpret_cast<const half8*>(src + i * ld_tok * dim);
+  u32x4* d = reinterpret_cast<u32x4*>(pool + o * dim);
+  for (int64_t p = (int64_t)blockIdx.y * 256 + threadIdx.x; p < nch; p += (int64_t)gridDim.y * 256) {
+    const half8 lo = s[2 * p], hi = s[2 * p + 1];
+    auto q4 = [](const half8& v, int k) {
+      return e4m3x4(256.f * (float)v[k], 256.f * (float)v[k + 1], 256.f * (float)v[k + 2], 256.f * (float)v[k + 3]);
+    };
+    d[p] = u32x4{q4(lo, 0), q4(lo, 4), q4(hi, 0), q4(hi, 4)};
+  }
+}
+
 }  // namespace
 
 void maxsim_check_args(int dim, int B, int ld_q, int K) {
@@ -237,11 +330,14 @@ void maxsim_check_args(int dim, int B, int ld_q, int K) {
   SR_CHECK(ld_q >= 1, "mv.score_rows: ld_q must be >= 1");
 }
 
-void launch_maxsim(const half_t* pool, const int64_t* off, const uint8_t* live, int64_t n_rows,
+void launch_maxsim(const void* pool, int dtype, const int64_t* off, const uint8_t* live, int64_t n_rows,
                    int dim, const half_t* q, const int32_t* q_len, int B, int ld_q,
                    const int64_t* rows, int K, float* out, double tokens_hint, hipStream_t s) {
   maxsim_check_args(dim, B, ld_q, K);
+  SR_CHECK(dtype == SR_DTYPE_F16 || dtype == SR_DTYPE_FP8_E4M3, "mv.score_rows: pool dtype");
   if (B == 0) return;
+  const bool fp8 = dtype == SR_DTYPE_FP8_E4M3;
+  const void* kernel = fp8 ? (const void*)maxsim_kernel<true> : (const void*)maxsim_kernel<false>;
   // candidates per workgroup: about 2048 workgroups (8 per CU) once there are that many pairs
   const int64_t pairs = (int64_t)B * K;
   const int cpw = (int)std::min<int64_t>(std::min<int64_t>(MV_MAXC, K), std::max<int64_t>(1, ceil_div(pairs, 2048)));
@@ -249,7 +345,7 @@ void launch_maxsim(const half_t* pool, const int64_t* off, const uint8_t* live, 
   SR_CHECK(grid < (1ll << 31), "mv.score_rows: too many pairs");
   const size_t smem = (size_t)MV_QT * round_up(dim, 128) * sizeof(half_t);
   // (per launch: the attribute belongs to the current device's copy of the kernel)
-  SR_HIP(hipFuncSetAttribute((const void*)maxsim_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+  SR_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                              MV_QT * 1024 * (int)sizeof(half_t)));
   MvArgs a;
   a.pool = pool;
@@ -265,8 +361,12 @@ void launch_maxsim(const half_t* pool, const int64_t* off, const uint8_t* live, 
   a.K = K;
   a.cpw = cpw;
   // (profiling only: the caller's estimate of the candidate tokens, 32 query tokens assumed)
-  ProfScope prof("maxsim", s, 2.0 * tokens_hint * dim * 32.0, tokens_hint * dim * 2.0 + (double)pairs * 12.0);
-  hipLaunchKernelGGL(maxsim_kernel, dim3((unsigned)grid), dim3(MV_THREADS), smem, s, a);
+  ProfScope prof(fp8 ? "maxsim_fp8" : "maxsim", s, 2.0 * tokens_hint * dim * 32.0,
+                 tokens_hint * dim * (fp8 ? 1.0 : 2.0) + (double)pairs * 12.0);
+  if (fp8)
+    hipLaunchKernelGGL(maxsim_kernel<true>, dim3((unsigned)grid), dim3(MV_THREADS), smem, s, a);
+  else
+    hipLaunchKernelGGL(maxsim_kernel<false>, dim3((unsigned)grid), dim3(MV_THREADS), smem, s, a);
   SR_LAUNCH_CHECK();
 }
 
@@ -277,6 +377,17 @@ void launch_mv_pack(const half_t* src, const int64_t* off, int64_t n, int ld_tok
   const int by = (int)std::min<int64_t>(64, std::max<int64_t>(1, ceil_div((int64_t)ld_tok * (dim >> 3), 256)));
   ProfScope prof("mv_pack", s, 0.0, (double)n * ld_tok * dim * 4.0);
   hipLaunchKernelGGL(mv_pack_kernel, dim3((unsigned)n, (unsigned)by), dim3(256), 0, s, src, off, ld_tok,
+                     dim, pool);
+  SR_LAUNCH_CHECK();
+}
+
+void launch_mv_pack_fp8(const half_t* src, const int64_t* off, int64_t n, int64_t ld_tok, int dim,
+                        uint8_t* pool, hipStream_t s) {
+  if (n <= 0) return;
+  SR_CHECK(n < (1ll << 31), "mv.add: too many rows in one call");
+  const int by = (int)std::min<int64_t>(1024, std::max<int64_t>(1, ceil_div(ld_tok * (dim >> 4), 256)));
+  ProfScope prof("mv_pack_fp8", s, 0.0, (double)n * ld_tok * dim * 3.0);
+  hipLaunchKernelGGL(mv_pack_fp8_kernel, dim3((unsigned)n, (unsigned)by), dim3(256), 0, s, src, off, ld_tok,
                      dim, pool);
   SR_LAUNCH_CHECK();
 }

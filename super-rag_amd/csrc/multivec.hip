@@ -1,10 +1,13 @@
 // Multi-vector index (sr_mv_*; DESIGN.md "Multi-vector retrieval"): the per-token unit vectors of
 // every row of a collection (bge-m3's multi-vector / ColBERT output), row-aligned with the store
-// like sr_lex.  One fp16 token pool [n_tokens][dim] in HBM, an int64 offsets array (device copy and
-// host mirror) and live flags; both the pool and the per-row arrays grow by doubling.  Appends and
+// like sr_lex.  One token pool [n_tokens][dim] in HBM, fp16 or (SR_DTYPE_FP8_E4M3) the bytes
+// e4m3(256 fp16(x)), an int64 offsets array (device copy and host mirror) and live flags; both the
+// pool and the per-row arrays grow by doubling.  Every way into an fp8 pool goes through the one
+// quantising kernel (launch_mv_pack_fp8), so the stored bytes do not depend on it.  Appends and
 // removals finish before they return; scoring (k_multivec.hip) is asynchronous on the caller's
 // stream and ordered against them by the completion event, as in the store.
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include "sr_kernels.h"
@@ -12,8 +15,9 @@
 
 namespace sr {
 
-MultiVecIndex::MultiVecIndex(int dim, int device) : dim_(dim), device_(device) {
+MultiVecIndex::MultiVecIndex(int dim, int device, int dtype) : dim_(dim), device_(device), dtype_(dtype) {
   SR_CHECK(dim >= 64 && dim <= 1024 && dim % 64 == 0, "mv: dim must be a multiple of 64, <= 1024");
+  SR_CHECK(dtype == SR_DTYPE_F16 || dtype == SR_DTYPE_FP8_E4M3, "mv: dtype must be SR_DTYPE_F16 or SR_DTYPE_FP8_E4M3");
   DeviceGuard g(device_);
   SR_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
   SR_HIP(hipEventCreateWithFlags(&done_, hipEventDisableTiming));
@@ -35,10 +39,9 @@ void MultiVecIndex::ensure_capacity(int64_t rows, int64_t tokens, hipStream_t s)
   if (tokens > cap_tokens_) {
     const int64_t cap = round_up(std::max<int64_t>(tokens, 2 * cap_tokens_), 1024);
     DevBuf np;
-    np.reserve((size_t)cap * dim_ * sizeof(half_t));
+    np.reserve((size_t)cap * row_bytes());
     if (n_tokens_ > 0)
-      SR_HIP(hipMemcpyAsync(np.p, pool_.p, (size_t)n_tokens_ * dim_ * sizeof(half_t),
-                            hipMemcpyDeviceToDevice, s));
+      SR_HIP(hipMemcpyAsync(np.p, pool_.p, (size_t)n_tokens_ * row_bytes(), hipMemcpyDeviceToDevice, s));
     SR_HIP(hipStreamSynchronize(s));
     std::swap(pool_.p, np.p);
     std::swap(pool_.bytes, np.bytes);
@@ -95,11 +98,24 @@ void MultiVecIndex::add_host(const int64_t* off, const float* vecs, int64_t n, i
   ensure_capacity(n_rows_ + n, n_tokens_ + T, stream_);
   if (T > 0) {
     float* stage;
+    half_t* h16;
+    int64_t* doff;
     Carve c;
     c.part((size_t)T * dim_, &stage);
+    c.part(fp8() ? (size_t)T * dim_ : 0, &h16);
+    c.part(fp8() ? 2 : 0, &doff);
     hostio_.carve(c);
     SR_HIP(hipMemcpyAsync(stage, vecs, (size_t)T * dim_ * sizeof(float), hipMemcpyHostToDevice, stream_));
-    launch_convert_f32_f16(stage, pool_.as<half_t>() + n_tokens_ * dim_, T * dim_, stream_);
+    if (fp8()) {
+      // fp32 -> fp16 as the fp16 pool stores it, then add_dev's quantiser over the T tokens as one row
+      const int64_t span[2] = {n_tokens_, n_tokens_ + T};
+      SR_HIP(hipMemcpyAsync(doff, span, sizeof(span), hipMemcpyHostToDevice, stream_));
+      launch_convert_f32_f16(stage, h16, T * dim_, stream_);
+      launch_mv_pack_fp8(h16, doff, 1, T, dim_, pool_.as<uint8_t>(), stream_);
+      SR_HIP(hipStreamSynchronize(stream_));  // `span` leaves scope
+    } else {
+      launch_convert_f32_f16(stage, pool_.as<half_t>() + n_tokens_ * dim_, T * dim_, stream_);
+    }
   }
   commit(len, stream_);
 }
@@ -127,7 +143,10 @@ void MultiVecIndex::add_dev(const half_t* vecs, const int32_t* len, int64_t n, i
   // the new rows' offsets first: the copy kernel reads them from the device array
   SR_HIP(hipMemcpyAsync(off_.as<int64_t>() + n_rows_, off.data(), (size_t)(n + 1) * sizeof(int64_t),
                         hipMemcpyHostToDevice, s));
-  launch_mv_pack(vecs, off_.as<int64_t>() + n_rows_, n, ld_tok, dim_, pool_.as<half_t>(), s);
+  if (fp8())
+    launch_mv_pack_fp8(vecs, off_.as<int64_t>() + n_rows_, n, ld_tok, dim_, pool_.as<uint8_t>(), s);
+  else
+    launch_mv_pack(vecs, off_.as<int64_t>() + n_rows_, n, ld_tok, dim_, pool_.as<half_t>(), s);
   SR_HIP(hipStreamSynchronize(s));  // `off` leaves scope
   commit(l64, s);
 }
@@ -156,6 +175,18 @@ void MultiVecIndex::stats(int64_t* n_rows, int64_t* n_live, int64_t* n_tokens) c
   if (n_tokens) *n_tokens = n_tokens_;
 }
 
+void MultiVecIndex::info(int* dtype, int64_t* pool_bytes) const {
+  if (dtype) *dtype = dtype_;
+  if (pool_bytes) *pool_bytes = n_tokens_ * (int64_t)row_bytes();
+}
+
+// value of an OCP e4m3fn byte (the pool never holds the NaN codes: the quantiser saturates)
+static float e4m3_value(uint8_t c) {
+  const int e = (c >> 3) & 15, m = c & 7;
+  const float a = e == 0 ? std::ldexp((float)m, -9) : std::ldexp((float)(8 + m), e - 10);
+  return (c & 0x80) ? -a : a;
+}
+
 void MultiVecIndex::get(int64_t row, float* out, int64_t cap, int64_t* n_tok) {
   SR_CHECK(row >= 0 && row < n_rows_, "mv.get: row out of range");
   const int64_t o = off_host_[(size_t)row], T = off_host_[(size_t)row + 1] - o;
@@ -166,6 +197,13 @@ void MultiVecIndex::get(int64_t row, float* out, int64_t cap, int64_t* n_tok) {
   SR_CHECK(out != nullptr, "mv.get: null output");
   DeviceGuard g(device_);
   begin(stream_);
+  if (fp8()) {  // the dequantised values e4m3_value / 256, exact in fp32
+    std::vector<uint8_t> h((size_t)m * dim_);
+    SR_HIP(hipMemcpyAsync(h.data(), pool_.as<uint8_t>() + o * dim_, h.size(), hipMemcpyDeviceToHost, stream_));
+    SR_HIP(hipStreamSynchronize(stream_));
+    for (size_t i = 0; i < h.size(); ++i) out[i] = e4m3_value(h[i]) * 0.00390625f;
+    return;
+  }
   std::vector<half_t> h((size_t)m * dim_);
   SR_HIP(hipMemcpyAsync(h.data(), pool_.as<half_t>() + o * dim_, h.size() * sizeof(half_t),
                         hipMemcpyDeviceToHost, stream_));
@@ -185,8 +223,8 @@ void MultiVecIndex::score_rows_dev(const half_t* q, const int32_t* q_len, int B,
     launch_fill_float(out, B * K, -INFINITY, s);
   } else {
     const double avg = (double)n_tokens_ / (double)n_rows_;
-    launch_maxsim(pool_.as<half_t>(), off_.as<int64_t>(), live_.as<uint8_t>(), n_rows_, dim_, q, q_len,
-                  B, ld_q, rows, K, out, avg * B * K, s);
+    launch_maxsim(pool_.p, dtype_, off_.as<int64_t>(), live_.as<uint8_t>(), n_rows_, dim_, q, q_len, B,
+                  ld_q, rows, K, out, avg * B * K, s);
   }
   end(s);
 }

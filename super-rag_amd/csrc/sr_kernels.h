@@ -284,12 +284,16 @@ void launch_score_rows(const half_t* corpus, int ld, int64_t n_rows, const uint8
 // [0, n_rows), dead or empty and for an empty query.  tokens_hint: candidate tokens, profiling only.
 // maxsim_check_args throws SR_ERR_INVALID outside the limits.  launch_mv_pack copies row i of src
 // [n][ld_tok][dim] (off[i + 1] - off[i] tokens) to pool + off[i] * dim.
+// dtype SR_DTYPE_FP8_E4M3: pool [n_tokens][dim] bytes e4m3(256 x), scored as the fp16 values d^ =
+// e4m3_value / 256 (the query stays fp16); launch_mv_pack_fp8 is launch_mv_pack into such a pool.
 void maxsim_check_args(int dim, int B, int ld_q, int K);
-void launch_maxsim(const half_t* pool, const int64_t* off, const uint8_t* live, int64_t n_rows,
+void launch_maxsim(const void* pool, int dtype, const int64_t* off, const uint8_t* live, int64_t n_rows,
                    int dim, const half_t* q, const int32_t* q_len, int B, int ld_q,
                    const int64_t* rows, int K, float* out, double tokens_hint, hipStream_t s);
 void launch_mv_pack(const half_t* src, const int64_t* off, int64_t n, int ld_tok, int dim,
                     half_t* pool, hipStream_t s);
+void launch_mv_pack_fp8(const half_t* src, const int64_t* off, int64_t n, int64_t ld_tok, int dim,
+                        uint8_t* pool, hipStream_t s);
 
 // k_lex.hip — reciprocal-rank fusion of two ranked row lists per query (-1 padded), fp64 scores.
 void launch_rrf_fuse(const int64_t* rows_a, int ka, const int64_t* rows_b, int kb, int B,

@@ -444,11 +444,12 @@ class LexIndex {
 };
 
 // ------------------------------------------------------------------------------------------------
-// Multi-vector index over the rows of a store (multivec.hip, k_multivec.hip): one fp16 token pool
-// [n_tokens][dim] in HBM, the first token of every row (int64) and live flags; scores are MaxSim.
+// Multi-vector index over the rows of a store (multivec.hip, k_multivec.hip): one token pool
+// [n_tokens][dim] in HBM (fp16, or e4m3 bytes of 256 x: dtype SR_DTYPE_FP8_E4M3), the first token of
+// every row (int64) and live flags; scores are MaxSim.
 class MultiVecIndex {
  public:
-  MultiVecIndex(int dim, int device);
+  MultiVecIndex(int dim, int device, int dtype = SR_DTYPE_F16);
   ~MultiVecIndex();
 
   int dim() const { return dim_; }
@@ -461,6 +462,9 @@ class MultiVecIndex {
                hipStream_t s);
   void remove(const int64_t* rows, int64_t n);
   void stats(int64_t* n_rows, int64_t* n_live, int64_t* n_tokens) const;
+  // the pool's dtype and the bytes of the stored tokens (not the capacity)
+  void info(int* dtype, int64_t* pool_bytes) const;
+  // fp32 values of the stored tokens (fp8: the dequantised ones)
   void get(int64_t row, float* out, int64_t cap, int64_t* n_tok);
   void score_rows_dev(const half_t* q, const int32_t* q_len, int B, int ld_q, const int64_t* rows,
                       int K, float* out, hipStream_t s);
@@ -477,7 +481,10 @@ class MultiVecIndex {
   // after the tokens are in the pool: offsets, live flags and the counts of n new rows
   void commit(const std::vector<int64_t>& len, hipStream_t s);
 
-  int dim_, device_;
+  bool fp8() const { return dtype_ == SR_DTYPE_FP8_E4M3; }
+  size_t row_bytes() const { return (size_t)dim_ * (fp8() ? 1 : sizeof(half_t)); }
+
+  int dim_, device_, dtype_;
   hipStream_t stream_ = nullptr;
   hipEvent_t done_ = nullptr;
   int64_t n_rows_ = 0, n_live_ = 0, n_tokens_ = 0, cap_rows_ = 0, cap_tokens_ = 0;

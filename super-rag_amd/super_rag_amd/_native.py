@@ -204,6 +204,8 @@ SIGNATURES = {
                                             c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                             c_void_p, c_void_p, c_void_p]),
     "sr_mv_create": (c_int, [c_int, c_int, POINTER(c_void_p)]),
+    "sr_mv_create_dtype": (c_int, [c_int, c_int, c_int, POINTER(c_void_p)]),
+    "sr_mv_info": (c_int, [c_void_p, POINTER(c_int), P_I64]),
     "sr_mv_add": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, P_I64]),
     "sr_mv_add_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, P_I64, c_void_p]),
     "sr_mv_remove": (c_int, [c_void_p, c_void_p, c_int64]),

@@ -2,10 +2,12 @@
 bge-m3 "dense + sparse + multi-vector" rerank of first-stage candidates.
 
 A document and a query are lists of per-token unit vectors (Encoder.embed_multivec); the score of a
-pair is MaxSim, ``(1 / Lq) * sum_i max_j q_i . d_j``, computed exactly on the fp16 values by the
+pair is MaxSim, ``(1 / Lq) * sum_i max_j q_i . d_j``, computed exactly on the stored values by the
 MFMA kernel of k_multivec.hip.  NativeMultiVectorIndex is row-aligned with the store like the
 lexical indexes: row i of the index is row i of the collection (DESIGN.md "Multi-vector
-retrieval").
+retrieval").  The tokens are stored as fp16 (the default) or, with ``dtype="fp8"``, as one OCP e4m3
+byte of ``256 x`` each: half the memory and half the bytes the kernel gathers, scored with the same
+definition on the dequantised values (the query stays fp16).
 """
 from __future__ import annotations
 
@@ -30,18 +32,37 @@ def pad_queries(q_vecs: Sequence, dim: int):
     return q, qlen
 
 
-class NativeMultiVectorIndex:
-    """Per-row token vectors resident in HBM of one device (sr_mv_*): one fp16 token pool, row
-    offsets and live flags.  ``dim`` is a multiple of 64, at most 1024."""
+MV_DTYPES = {"fp16": N.SR_DTYPE_F16, "fp8": N.SR_DTYPE_FP8_E4M3}
 
-    def __init__(self, dim: int, device: int = 0):
+
+class NativeMultiVectorIndex:
+    """Per-row token vectors resident in HBM of one device (sr_mv_*): one token pool, row offsets
+    and live flags.  ``dim`` is a multiple of 64, at most 1024.  ``dtype``: "fp16", or "fp8" for
+    e4m3(256 x) bytes (unit-norm tokens; an element past 1.75 in magnitude saturates)."""
+
+    def __init__(self, dim: int, device: int = 0, dtype: str = "fp16"):
         self._h = None
+        if dtype not in MV_DTYPES:
+            raise ValueError(f"dtype must be one of {sorted(MV_DTYPES)}, got {dtype!r}")
         N.require_gpu()
         h = ctypes.c_void_p()
-        N.call("sr_mv_create", int(dim), int(device), ctypes.byref(h))
+        N.call("sr_mv_create_dtype", int(dim), int(device), MV_DTYPES[dtype], ctypes.byref(h))
         self._h = h
         self.dim = int(dim)
         self.device = int(device)
+        self._dtype = dtype
+
+    @property
+    def dtype(self) -> str:
+        """"fp16" or "fp8": how the tokens are stored."""
+        return self._dtype
+
+    @property
+    def nbytes(self) -> int:
+        """Bytes of the stored tokens (sr_mv_info: tokens * dim * element size, not the capacity)."""
+        n = ctypes.c_int64(0)
+        N.call("sr_mv_info", self._h, None, ctypes.byref(n))
+        return int(n.value)
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -55,8 +76,8 @@ class NativeMultiVectorIndex:
             pass
 
     def add(self, docs: Sequence) -> int:
-        """Append rows, each an array [n_tokens, dim] (fp32, rounded to fp16; 0 tokens allowed);
-        returns the first row id."""
+        """Append rows, each an array [n_tokens, dim] (fp32, rounded to fp16, then quantised on an
+        fp8 index; 0 tokens allowed); returns the first row id."""
         arrs = [np.asarray(d, dtype=np.float32).reshape(-1, self.dim) for d in docs]
         off = np.zeros(len(arrs) + 1, dtype=np.int64)
         if arrs:
@@ -93,7 +114,7 @@ class NativeMultiVectorIndex:
         return {"rows": int(n.value), "live": int(live.value), "tokens": int(tok.value)}
 
     def get(self, row: int) -> np.ndarray:
-        """The stored fp16 token vectors of a row, as fp32 [n_tokens, dim]."""
+        """The stored token vectors of a row (fp8: dequantised), as fp32 [n_tokens, dim]."""
         n = ctypes.c_int64(0)
         N.call("sr_mv_get", self._h, int(row), None, 0, ctypes.byref(n))
         out = np.empty((int(n.value), self.dim), dtype=np.float32)

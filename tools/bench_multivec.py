@@ -2,7 +2,7 @@
 the headline bench.py line.
 
     python tools/bench_multivec.py [--repeats 9] [--pool-tokens 1048576] [--skip-encoder]
-                                   [--out profiles/multivec_bench.json]
+                                   [--dtype fp16|fp8|both] [--out profiles/multivec_bench.json]
 
 Part 1, sr_mv_score_rows_dev at the (B, K, dim, Lq, Ld) shapes of SHAPES: an index of pool-tokens / Ld
 rows of Ld random unit tokens (so nothing is cache-resident by construction: 2 GiB at dim 1024), random
@@ -10,6 +10,11 @@ candidate rows, random unit queries.  Per shape: the time, the bytes of candidat
 dim 2, once per 64-token query block) and that rate as a fraction of the library's copy yardstick
 (sr_diag_copy, read + written bytes, measured in the same process); both rates come from the wall time
 of whole calls, and the kernel's own rate from the profiler's events is reported next to them.
+--dtype picks the index's storage (fp16, the default, or fp8: bytes per token dim instead of 2 dim); with
+"both" the two indices are built over the same tokens and the same queries and candidate lists are timed on
+each in the same process, per shape fp16 first (the yardstick of the comparison is that run, not an earlier
+figure): the record then holds both call times with their min-max, the ratio fp16 / fp8 and the fp8 rate on
+fp8 bytes against the copy yardstick, and goes to profiles/multivec_fp8_bench.json.
 Part 2, the head's cost: embed_multivec_dev against embed_sparse_dev and embed_dev (mean pooling, so all
 three run the full last layer) on bge-m3's shape with seeded weights (vocabulary cut to --vocab rows), at
 B = 64, S = 512 and B = 2, S = 8192, with the two added kernels' own times from the profiler.
@@ -74,42 +79,84 @@ def unit_rows(shape, gen):
     return (x / x.norm(dim=-1, keepdim=True)).to(torch.float16)
 
 
+KERNEL = {"fp16": "maxsim", "fp8": "maxsim_fp8"}
+ELEMENT_BYTES = {"fp16": 2, "fp8": 1}
+
+
+def time_shape(x, dtype, shape, q, qlen, rows, n, copy_gbs, repeats):
+    """One shape on one index: the record of the single-dtype table."""
+    B, K, dim, Lq, Ld = shape
+    score = torch.empty((B, K), dtype=torch.float32, device="cuda")
+    ms = median_ms(lambda: x.score_rows_dev(q, qlen, rows, out=score), repeats)
+    name = KERNEL[dtype]
+    k = kernel_ms(lambda: x.score_rows_dev(q, qlen, rows, out=score), (name,), repeats)[name]
+    blocks = (Lq + 63) // 64
+    nbytes = float(B) * K * Ld * dim * ELEMENT_BYTES[dtype] * blocks
+    rate = lambda t_ms: nbytes / (t_ms * 1e-3) / 1e9
+    return {"B": B, "K": K, "dim": dim, "Lq": Lq, "Ld": Ld, "pool_rows": n,
+            "ms": round(ms[0], 4), "min_max_ms": [round(ms[1], 4), round(ms[2], 4)],
+            "kernel_ms": None if k is None else round(k, 4),
+            "candidate_bytes": nbytes, "query_blocks": blocks,
+            # the call's wall time, as the copy yardstick is timed; the kernel's own rate apart
+            "GBs": round(rate(ms[0]), 1), "fraction_of_copy": round(rate(ms[0]) / copy_gbs, 3),
+            "kernel_GBs": None if k is None else round(rate(k), 1),
+            "TFs": round(2.0 * B * K * Ld * Lq * dim / (ms[0] * 1e-3) / 1e12, 1),
+            "finite": bool(torch.isfinite(score).all().item())}, score
+
+
 def bench_maxsim(a, copy_gbs):
     gen = torch.Generator(device="cuda")
     gen.manual_seed(0)
+    dtypes = ["fp16", "fp8"] if a.dtype == "both" else [a.dtype]
     out, cache = [], {}
-    for B, K, dim, Lq, Ld in SHAPES:
+    for shape in SHAPES:
+        B, K, dim, Lq, Ld = shape
         if (dim, Ld) not in cache:
-            cache.clear()                                     # one pool at a time
+            for xs, _ in cache.values():                      # one pool per dtype at a time
+                for x in xs.values():
+                    x.close()
+            cache.clear()
             n = max(K, a.pool_tokens // Ld)
-            x = NativeMultiVectorIndex(dim)
-            step = max(1, (1 << 28) // (Ld * dim * 2))        # 256 MiB of tokens per add
+            xs = {d: NativeMultiVectorIndex(dim, dtype=d) for d in dtypes}
+            step = max(1, (1 << 28) // (Ld * dim * 2))        # 256 MiB of fp16 tokens per add
             for i in range(0, n, step):
                 m = min(step, n - i)
-                x.add_dev(unit_rows((m, Ld, dim), gen), torch.full((m,), Ld, dtype=torch.int32, device="cuda"))
-            cache[(dim, Ld)] = (x, n)
-        x, n = cache[(dim, Ld)]
+                toks = unit_rows((m, Ld, dim), gen)           # the same tokens into every index
+                lens = torch.full((m,), Ld, dtype=torch.int32, device="cuda")
+                for x in xs.values():
+                    x.add_dev(toks, lens)
+            cache[(dim, Ld)] = (xs, n)
+        xs, n = cache[(dim, Ld)]
         q = unit_rows((B, Lq, dim), gen)
         qlen = torch.full((B,), Lq, dtype=torch.int32, device="cuda")
         rows = torch.randint(0, n, (B, K), dtype=torch.int64, device="cuda", generator=gen)
-        score = torch.empty((B, K), dtype=torch.float32, device="cuda")
-        ms = median_ms(lambda: x.score_rows_dev(q, qlen, rows, out=score), a.repeats)
-        k = kernel_ms(lambda: x.score_rows_dev(q, qlen, rows, out=score), ("maxsim",), a.repeats)
-        blocks = (Lq + 63) // 64
-        nbytes = float(B) * K * Ld * dim * 2 * blocks
-        rate = lambda t_ms: nbytes / (t_ms * 1e-3) / 1e9
+        rec, score = {}, {}
+        for d in dtypes:
+            rec[d], score[d] = time_shape(xs[d], d, shape, q, qlen, rows, n, copy_gbs, a.repeats)
+            print("# maxsim", d, rec[d], flush=True)
+        if a.dtype != "both":
+            out.append(rec[a.dtype])
+            continue
+        r16, r8 = rec["fp16"], rec["fp8"]
+        spread = max(r16["min_max_ms"][1] - r16["min_max_ms"][0], r8["min_max_ms"][1] - r8["min_max_ms"][0])
         out.append({"B": B, "K": K, "dim": dim, "Lq": Lq, "Ld": Ld, "pool_rows": n,
-                    "ms": round(ms[0], 4), "min_max_ms": [round(ms[1], 4), round(ms[2], 4)],
-                    "kernel_ms": None if k["maxsim"] is None else round(k["maxsim"], 4),
-                    "candidate_bytes": nbytes, "query_blocks": blocks,
-                    # the call's wall time, as the copy yardstick is timed; the kernel's own rate apart
-                    "GBs": round(rate(ms[0]), 1), "fraction_of_copy": round(rate(ms[0]) / copy_gbs, 3),
-                    "kernel_GBs": None if k["maxsim"] is None else round(rate(k["maxsim"]), 1),
-                    "TFs": round(2.0 * B * K * Ld * Lq * dim / (ms[0] * 1e-3) / 1e12, 1),
-                    "finite": bool(torch.isfinite(score).all().item())})
-        print("# maxsim", out[-1], flush=True)
-    for x, _ in cache.values():
-        x.close()
+                    "fp16_ms": r16["ms"], "fp16_min_max_ms": r16["min_max_ms"], "fp16_kernel_ms": r16["kernel_ms"],
+                    "fp8_ms": r8["ms"], "fp8_min_max_ms": r8["min_max_ms"], "fp8_kernel_ms": r8["kernel_ms"],
+                    "fp16_over_fp8": round(r16["ms"] / r8["ms"], 3),
+                    "kernel_fp16_over_fp8": (None if not (r16["kernel_ms"] and r8["kernel_ms"])
+                                             else round(r16["kernel_ms"] / r8["kernel_ms"], 3)),
+                    # fp8 slower than fp16 by more than the wider of the two recorded min-max spreads?
+                    "spread_ms": round(spread, 4), "fp8_not_slower": bool(r8["ms"] <= r16["ms"] + spread),
+                    "fp16_GBs": r16["GBs"], "fp16_fraction_of_copy": r16["fraction_of_copy"],
+                    "fp8_candidate_bytes": r8["candidate_bytes"], "fp8_GBs": r8["GBs"],
+                    "fp8_fraction_of_copy": r8["fraction_of_copy"], "fp8_kernel_GBs": r8["kernel_GBs"],
+                    "fp8_TFs": r8["TFs"],
+                    "max_abs_score_diff": float((score["fp16"] - score["fp8"]).abs().max().item()),
+                    "finite": r16["finite"] and r8["finite"]})
+        print("# maxsim both", out[-1], flush=True)
+    for xs, _ in cache.values():
+        for x in xs.values():
+            x.close()
     return out
 
 
@@ -151,14 +198,19 @@ def main():
     ap.add_argument("--vocab", type=int, default=32000, help="encoder vocabulary rows (bge-m3: 250002)")
     ap.add_argument("--max-tokens", type=int, default=32768)
     ap.add_argument("--skip-encoder", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "multivec_bench.json"))
+    ap.add_argument("--dtype", choices=("fp16", "fp8", "both"), default="fp16",
+                    help="token storage of the index; both: fp16 and fp8 over the same tokens, compared")
+    ap.add_argument("--out", default=None,
+                    help="default profiles/multivec_bench.json, profiles/multivec_fp8_bench.json with --dtype both")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "multivec_fp8_bench.json" if a.dtype == "both" else "multivec_bench.json")
     os.environ.setdefault("SUPER_RAG_AMD_SYNTHETIC", "1")
     N.require_gpu()
     copy_gbs = copy_yardstick_gbs(1 << 28, a.repeats)
     rec = {"metric": "sr_mv_score_rows_dev against the copy yardstick; multi-vector forward vs sparse / plain",
            "repeats": a.repeats, "statistic": "median of repeats after one warm-up call",
-           "copy_yardstick_GBs": round(copy_gbs, 1), "pool_tokens": a.pool_tokens}
+           "copy_yardstick_GBs": round(copy_gbs, 1), "pool_tokens": a.pool_tokens, "dtype": a.dtype}
     rec["maxsim"] = bench_maxsim(a, copy_gbs)
     if not a.skip_encoder:
         rec["forward"] = bench_forward(a)
