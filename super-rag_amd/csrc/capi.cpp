@@ -1188,8 +1188,8 @@ int sr_encoder_forward_sparse(sr_encoder* e, const int32_t* ids, const int32_t* 
   SR_NONNULL(e);
   if (n_special > 0) SR_NONNULL(special_ids);
   std::lock_guard<std::mutex> lk(e->impl->mu);
-  e->impl->forward_sparse_host(ids, mask, type_ids, B, S, pool, out_dense, special_ids, n_special,
-                               out_tok_weight, out_terms, out_weights, out_count);
+  const sr::Encoder::SparseOut so{special_ids, n_special, out_tok_weight, out_terms, out_weights, out_count};
+  e->impl->forward_host(ids, mask, type_ids, B, S, 0, pool, out_dense, &so);
   SR_API_END
 }
 
@@ -1241,10 +1241,14 @@ int sr_encoder_forward_multivec(sr_encoder* e, const int32_t* ids, const int32_t
   SR_API_BEGIN
   SR_NONNULL(e);
   if (out_terms && n_special > 0) SR_NONNULL(special_ids);
+  const bool any_sparse = out_tok_weight || out_terms || out_weights || out_count;
+  const bool with_sparse = out_terms && out_weights && out_count;
+  SR_CHECK(!any_sparse || with_sparse,
+           "encoder: the sparse outputs are one group: terms, weights and count together or none");
   std::lock_guard<std::mutex> lk(e->impl->mu);
-  e->impl->forward_multivec_host(ids, mask, type_ids, B, S, pool, out_dense, out_vecs, out_len,
-                                 special_ids, n_special, out_tok_weight, out_terms, out_weights,
-                                 out_count);
+  const sr::Encoder::SparseOut so{special_ids, n_special, out_tok_weight, out_terms, out_weights, out_count};
+  const sr::Encoder::MultiVecHost mo{out_vecs, out_len};
+  e->impl->forward_host(ids, mask, type_ids, B, S, 0, pool, out_dense, with_sparse ? &so : nullptr, &mo);
   SR_API_END
 }
 

@@ -215,6 +215,12 @@ void Encoder::set_weight(const std::string& name, const float* data, int64_t num
   fold_ready_ = false;
 }
 
+// an A/B switch of the environment: on unless set to 0
+static bool switch_on(const char* name) {
+  const char* e = std::getenv(name);
+  return !(e && e[0] == '0');
+}
+
 // LayerNorm folding: with an fp16 residual stream the two LayerNorms of a block are
 // never materialised.  The GEMM that produces a residual sum u also writes per-row Chan partial
 // statistics; the next GEMM consumes u itself with LN(u) = (u - mu) rstd gamma + beta folded in:
@@ -223,44 +229,49 @@ void Encoder::set_weight(const std::string& name, const float* data, int64_t num
 bool Encoder::fold_enabled() const {
   if (!cfg_.residual_fp16) return false;
   if (cfg_.hidden % 256 != 0 || cfg_.intermediate % 256 != 0) return false;
-  const char* e = std::getenv("SR_LN_FOLD");
-  return !(e && e[0] == '0');
+  return switch_on("SR_LN_FOLD");
 }
 
 // K5c (fused QKV projection + attention) for the folded layers at S == 128; SR_FUSED_QKV_ATTN=0
 // keeps the QKV GEMM + K5b pair (bit-identical results; A/B tests).  Same-box bench: 461.2 vs
 // 454.3 q/s (profiles/r02_fused_qkv_attention/).
-static bool fused_qkv_attention_enabled() {
-  const char* e = std::getenv("SR_FUSED_QKV_ATTN");
-  return !(e && e[0] == '0');
-}
+static bool fused_qkv_attention_enabled() { return switch_on("SR_FUSED_QKV_ATTN"); }
 
 // K/V-free CLS-only last layer of the folded cross-encoders (cls_attn_fold, k_encoder_misc.hip):
 // no K / V projection of the S tokens; SR_KVFREE_CLS=0 keeps the K, V GEMM + CLS attention (A/B).
-static bool kvfree_cls_enabled() {
-  const char* e = std::getenv("SR_KVFREE_CLS");
-  return !(e && e[0] == '0');
+static bool kvfree_cls_enabled() { return switch_on("SR_KVFREE_CLS"); }
+
+// The fp8 modes (sr_runtime.h, set_fp8) as the GEMMs of a folded layer that run in fp8
+Encoder::Fp8Plan Encoder::fp8_plan(int mode) {
+  SR_CHECK((mode >= 0 && mode <= 3) || (SR_WITH_DIAG && mode >= 4 && mode <= 5),
+           "encoder: fp8 mode must be 0 .. 3 (modes 4 / 5 were rejected: diagnostic library only)");
+  Fp8Plan p;
+  p.ffn2 = mode >= 1;
+  p.ffn1 = mode >= 2;
+  p.qkv = mode == 2 || mode == 4;
+  p.qkv_norm = mode == 4;
+  p.oproj = mode == 5;
+  return p;
 }
 
 void Encoder::set_fp8(int mode) {
-  // Product modes: 0 (fp16), 1 (FFN2 fp8), 3 (FFN1 + FFN2 fp8; rank like the fp32 oracle on the
-  // discriminative fidelity sets) and the opt-in speed / fidelity trade 2 (also the QKV of layers
-  // >= 1 in fp8 on the e4m3 residual copy: std / err 2.0).  Measured and rejected (the
-  // diagnostic library keeps them for the record): 4 (QKV in fp8 on normalised e4m3 rows: 2.0) and
-  // 5 (mode 3 + the O-projection of the fused layers on e4m3 ctx written by K5c: 6.4).
-  SR_CHECK((mode >= 0 && mode <= 3) || (SR_WITH_DIAG && mode >= 4 && mode <= 5),
-           "encoder: fp8 mode must be 0 .. 3 (modes 4 / 5 were rejected: diagnostic library only)");
-  if (mode) {
+  const Fp8Plan p = fp8_plan(mode);
+  if (p.ffn2) {  // every fp8 mode runs FFN2 (K = intermediate) in fp8; the others have K = hidden
     SR_CHECK(fold_enabled(), "encoder: fp8 modes need the LN-folded fp16-residual path");
     SR_CHECK(cfg_.intermediate % 128 == 0 && cfg_.intermediate >= 256 &&
-                 (mode < 2 || (cfg_.hidden % 128 == 0 && cfg_.hidden >= 256)),
+                 (!(p.ffn1 || p.qkv || p.oproj) || (cfg_.hidden % 128 == 0 && cfg_.hidden >= 256)),
              "encoder: fp8 GEMMs need K % 128 == 0, K >= 256");
   }
   if (mode != fp8_) {
     fp8_ = mode;
+    plan_ = p;
     fold_ready_ = false;  // re-derive the folded weights (and their e4m3 copies)
   }
 }
+
+// The folded weights serve every S: prepare_fold asks for the K/V-free form at the rerank pair
+// length (hidden and heads decide it; forward_dev asks again with the S it runs)
+static constexpr int kKvfreePrepS = 128;
 
 void Encoder::prepare_fold(hipStream_t s) {
   if (fold_ready_) return;
@@ -275,13 +286,13 @@ void Encoder::prepare_fold(hipStream_t s) {
                           L.d1.as<float>(), s);
     L.w2h.reserve((size_t)D * F * sizeof(half_t));  // 0.5 W2: FFN1 stores 2 GELU (exact scale)
     launch_scale_f16(L.w2.as<half_t>(), 0.5f, L.w2h.as<half_t>(), D * F, s);
-    if (fp8_ >= 1) {
+    if (plan_.ffn2) {
       L.w2_8.reserve((size_t)D * F);
       L.w2e.reserve((size_t)D);
       launch_quantize_rows_fp8(L.w2h.as<half_t>(), (int)D, (int)F, L.w2_8.as<uint8_t>(),
                                L.w2e.as<uint8_t>(), s);
     }
-    if (fp8_ >= 2) {
+    if (plan_.ffn1) {
       L.w1_8.reserve((size_t)F * D);
       L.w1e.reserve((size_t)F);
       L.c1_8.reserve((size_t)F * sizeof(float));
@@ -290,7 +301,7 @@ void Encoder::prepare_fold(hipStream_t s) {
       launch_colsum_fp8(L.w1_8.as<uint8_t>(), L.w1e.as<uint8_t>(), (int)F, (int)D,
                         L.c1_8.as<float>(), s);
     }
-    if (fp8_ == 5) {
+    if (plan_.oproj) {
       L.wo_8.reserve((size_t)D * D);
       L.woe.reserve((size_t)D);
       launch_quantize_rows_fp8(L.wo.as<half_t>(), (int)D, (int)D, L.wo_8.as<uint8_t>(),
@@ -301,7 +312,7 @@ void Encoder::prepare_fold(hipStream_t s) {
     if (l == 0) continue;  // layer 0 reads the (normalised) embedding LayerNorm output
     const Layer& P = layers_[l - 1];
     const bool kvfree_prep = l + 1 == layers_.size() && kvfree_cls_enabled() &&
-                             cls_attn_fold_supported(128, (int)D, cfg_.heads);
+                             cls_attn_fold_supported(kKvfreePrepS, (int)D, cfg_.heads);
     L.bo_f.reserve((size_t)D * sizeof(float));  // O-proj bias + beta of the previous LN2
     launch_vec_add(L.bo.as<float>(), P.ln2b.as<float>(), L.bo_f.as<float>(), (int)D, s);
     L.wqkv_f.reserve((size_t)3 * D * D * sizeof(half_t));
@@ -319,7 +330,7 @@ void Encoder::prepare_fold(hipStream_t s) {
       launch_kv_blockdiag(L.wqkv_f.as<half_t>(), (int)D, cfg_.heads, L.wk_bd.as<half_t>(),
                           L.wv_bd.as<half_t>(), s);
     }
-    if (fp8_ == 2 || fp8_ == 4) {
+    if (plan_.qkv) {
       L.wqkv8.reserve((size_t)3 * D * D);
       L.wqkve.reserve((size_t)3 * D);
       L.cqkv8.reserve((size_t)3 * D * sizeof(float));
@@ -329,7 +340,7 @@ void Encoder::prepare_fold(hipStream_t s) {
                         L.cqkv8.as<float>(), s);
     }
   }
-  if (fp8_ == 4) {  // (mu, rstd) = (0, 1) for every row: mode 4's QKV reads normalised rows
+  if (plan_.qkv_norm) {  // (mu, rstd) = (0, 1) for every row: this QKV reads normalised rows
     unit_mr_.reserve(2 * sizeof(float));
     const float one[2] = {0.f, 1.f};
     SR_HIP(hipMemcpyAsync(unit_mr_.p, one, sizeof(one), hipMemcpyHostToDevice, s));
@@ -344,7 +355,7 @@ std::string Encoder::missing() const {
   return std::string();
 }
 
-void Encoder::ensure_ws(int64_t tokens, int B) {
+void Encoder::ensure_ws(int64_t tokens) {
   if (tokens <= ws_tokens_) return;
   SR_HIP(hipEventSynchronize(done_));  // the previous call may still use the old workspace
   const int64_t d = cfg_.hidden, F = cfg_.intermediate;
@@ -367,13 +378,11 @@ void Encoder::ensure_ws(int64_t tokens, int B) {
     mrA_.reserve((size_t)tokens * 2 * sizeof(float));
     mrB_.reserve((size_t)tokens * 2 * sizeof(float));
   }
-  (void)B;
   ws_tokens_ = tokens;
 }
 
-void Encoder::forward_dev(const int32_t* ids, const int32_t* mask, const int32_t* types, int B,
-                          int S, int mode, int pool, void* out, int out_dtype, int ld_out,
-                          hipStream_t s, const TokenHeads* heads) {
+void Encoder::check_forward(int B, int S, int mode, int pool, int out_dtype, int ld_out,
+                            const TokenHeads* heads) const {
   SR_CHECK(B >= 0 && S >= 1, "encoder: bad batch shape");
   const SparseOut* sparse = heads ? heads->sparse : nullptr;
   const MultiVecOut* mv = heads ? heads->multivec : nullptr;
@@ -403,373 +412,388 @@ void Encoder::forward_dev(const int32_t* ids, const int32_t* mask, const int32_t
     throw Error(SR_ERR_STATE, std::string("encoder: weight not set: colbert_linear.") +
                                   (colbert_w_set_ ? "bias" : "weight"));
   if (mv) colbert_pack_check_args(B, S, colbert_dc_);
-  if (B == 0) return;
-  DeviceGuard g(device_);
-  // s == nullptr is the HIP null stream (torch's default stream): use it as-is.
-  begin(s);
-  const int d = cfg_.hidden, F = cfg_.intermediate, H = cfg_.heads;
-  const int64_t seqs_per_chunk = std::max<int64_t>(1, max_tokens_ / S);
-  const int64_t chunk_tokens = std::min<int64_t>((int64_t)B, seqs_per_chunk) * S;
-  ensure_ws(chunk_tokens, B);
-  if (mode == 1 && clst_.bytes < (size_t)std::min<int64_t>(B, seqs_per_chunk) * d * sizeof(float))
-    SR_HIP(hipEventSynchronize(done_));
-  if (mode == 1) clst_.reserve((size_t)std::min<int64_t>(B, seqs_per_chunk) * d * sizeof(float));
+}
+
+// The workspaces of one call with launch chunks of chunk_seqs sequences; returns where the sparse
+// head's token weights go.  A buffer that has to grow first waits for done_: the previous call may
+// still use the old one.
+float* Encoder::reserve_forward(int B, int S, int mode, int64_t chunk_seqs, const TokenHeads* heads) {
+  const SparseOut* sparse = heads ? heads->sparse : nullptr;
+  ensure_ws(chunk_seqs * S);
+  if (mode == 1) {
+    const size_t need = (size_t)chunk_seqs * cfg_.hidden * sizeof(float);
+    if (clst_.bytes < need) SR_HIP(hipEventSynchronize(done_));
+    clst_.reserve(need);
+  }
   float* tok_weight = sparse ? sparse->tok_weight : nullptr;
   if (sparse && !tok_weight) {
     if (sparse_tw_.bytes < (size_t)B * S * sizeof(float)) SR_HIP(hipEventSynchronize(done_));
     sparse_tw_.reserve((size_t)B * S * sizeof(float));
     tok_weight = sparse_tw_.as<float>();
   }
-  if (mv) {  // the head's GEMM output of one launch chunk
-    const size_t need = (size_t)chunk_tokens * colbert_dc_ * sizeof(half_t);
+  if (heads && heads->multivec) {  // the head's GEMM output of one launch chunk
+    const size_t need = (size_t)chunk_seqs * S * colbert_dc_ * sizeof(half_t);
     if (colbert_v_.bytes < need) SR_HIP(hipEventSynchronize(done_));
     colbert_v_.reserve(need);
   }
-  half_t* h16 = h16_.as<half_t>();
-  float* h32 = h32_.as<float>();
-  half_t* qkv = qkv_.as<half_t>();
-  half_t* ctx = ctx_.as<half_t>();
-  void* y = y32_.p;  // bias + residual sum: fp32, or fp16 with an fp16 residual stream
-  half_t* ffn = ffn_.as<half_t>();
-  int32_t* pos = pos_.as<int32_t>();
-  const bool res16 = cfg_.residual_fp16 != 0;
-  const void* hres = res16 ? (const void*)h16 : (const void*)h32;  // residual operand
-  float* h32w = res16 ? nullptr : h32;
-  const int epi_res = res16 ? EPI_BIAS_RES_F16 : EPI_BIAS_RES_F32;
+  return tok_weight;
+}
+
+void Encoder::forward_dev(const int32_t* ids, const int32_t* mask, const int32_t* types, int B,
+                          int S, int mode, int pool, void* out, int out_dtype, int ld_out,
+                          hipStream_t s, const TokenHeads* heads) {
+  check_forward(B, S, mode, pool, out_dtype, ld_out, heads);
+  if (B == 0) return;
+  DeviceGuard g(device_);
+  // s == nullptr is the HIP null stream (torch's default stream): use it as-is.
+  begin(s);
+  const int d = cfg_.hidden, H = cfg_.heads;
+  const int64_t seqs_per_chunk = std::max<int64_t>(1, max_tokens_ / S);
+  float* tok_weight = reserve_forward(B, S, mode, std::min<int64_t>(B, seqs_per_chunk), heads);
+  const bool fold = fold_enabled();
+  if (fold) prepare_fold(s);
+
+  Chunk c{};
+  c.S = S;
+  c.s = s;
   // Only the first token's final state is consumed (CLS pooling / classification head): the last
   // layer runs attention for query row 0 only and its O-projection, LayerNorms and FFN on the
   // B CLS rows (exact: every other row of the last layer is dead).
   // The token heads read every token's final state: their request keeps the full last layer.
-  const bool cls_only = !heads && ((mode == 1) || (pool == SR_POOL_CLS));
-
-  const bool fold = fold_enabled();
-  if (fold) prepare_fold(s);
-  const int nparts = d / 128;
-
+  c.cls_only = !heads && ((mode == 1) || (pool == SR_POOL_CLS));
+  if (fold) {
+    c.U = h16_.as<half_t>();
+    c.Uc = y32_.as<half_t>();
+    c.sA = statA_.as<float>();
+    c.sB = statB_.as<float>();
+    c.mA = mrA_.as<float>();
+    c.mB = mrB_.as<float>();
+    c.u8 = u8_.as<uint8_t>();
+    // K5c: QKV projection + attention in one kernel (the QKV activation stays in LDS); an fp8 QKV
+    // projection runs unfused
+    c.fuse_qa = fused_qkv_attention_enabled() && !plan_.qkv && qkv_attention_supported(S, d, H);
+    // the fused layers' ctx as e4m3 (in the FFN buffer, dead until this layer's FFN1) and their
+    // O-projection on the fp8 MFMA
+    c.o8 = plan_.oproj && c.fuse_qa;
+    c.ctx8 = ffn_.as<uint8_t>();
+    // (an fp8 QKV projection keeps the e4m3 QKV path in every layer)
+    c.kvfree = c.cls_only && !plan_.qkv && kvfree_cls_enabled() && layers_.size() > 1 &&
+               cls_attn_fold_supported(S, d, H) && layers_.back().wk_bd.p != nullptr;
+  }
   for (int64_t b0 = 0; b0 < B; b0 += seqs_per_chunk) {
-    const int nb = (int)std::min<int64_t>(seqs_per_chunk, B - b0);
-    const int M = nb * S;
-    const int32_t* cids = ids + b0 * S;
-    const int32_t* cmask = mask + b0 * S;
-    const int32_t* ctypes = types ? types + b0 * S : nullptr;
-    launch_positions(cids, pos, nb, S, cfg_.position_offset, s);
-    launch_embed_ln(cids, pos, ctypes, wemb_.as<half_t>(), pemb_.as<half_t>(), temb_.as<half_t>(),
-                    embg_.as<float>(), embb_.as<float>(), cfg_.ln_eps, M, d, cfg_.vocab_size,
-                    cfg_.max_position, cfg_.type_vocab, h16, h32w, s);
-    if (fold) {
-      // u (un-normalised residual sums) lives in h16 (in place); compact last-layer rows in y32_.
-      // sA / mrA: statistics of u after the O-projection, sB / mrB: after FFN2.
-      half_t* U = h16;
-      half_t* Uc = reinterpret_cast<half_t*>(y);
-      float* sA = statA_.as<float>();
-      float* sB = statB_.as<float>();
-      float* mA = mrA_.as<float>();
-      float* mB = mrB_.as<float>();
-      uint8_t* u8 = u8_.as<uint8_t>();
-      // K5c: QKV projection + attention in one kernel (the QKV activation stays in LDS)
-      // fp8 modes: 2 and 3 run FFN1 (and FFN2) on e4m3 copies of the residual sums, mode 2 also the
-      // QKV projection of layers >= 1 (then unfused); mode 3 keeps QKV + attention in fp16 (K5c)
-      // mode 4 = mode 3 + the QKV projection of layers >= 1 in fp8 on an e4m3 copy of the
-      // NORMALISED rows (u - mu) rstd (its own pass after the row statistics; unfused)
-      const bool ffn1_8 = fp8_ >= 2, qkv_8 = fp8_ == 2 || fp8_ == 4, qkv_norm8 = fp8_ == 4;
-      const bool fuse_qa = fused_qkv_attention_enabled() && !qkv_8 && qkv_attention_supported(S, d, H);
-      // mode 5: the fused layers' ctx as e4m3 (in the FFN buffer, dead until this layer's FFN1)
-      // and their O-projection on the fp8 MFMA
-      const bool o8 = fp8_ == 5 && fuse_qa;
-      uint8_t* ctx8 = reinterpret_cast<uint8_t*>(ffn);
-      // (qkv_8: mode 2 keeps the e4m3 QKV path in every layer)
-      const bool kvfree = cls_only && !qkv_8 && kvfree_cls_enabled() && layers_.size() > 1 &&
-                          cls_attn_fold_supported(S, d, H) && layers_.back().wk_bd.p != nullptr;
-      for (size_t l = 0; l < layers_.size(); ++l) {
-        const Layer& L = layers_[l];
-        const bool last = cls_only && l + 1 == layers_.size();
-        const Layer* P = l > 0 ? &layers_[l - 1] : nullptr;
-        if (fuse_qa && !last) {
-          LnFold lq;
-          lq.mr = mB;
-          lq.colsum = L.cqkv.as<float>();
-          if (l == 0)
-            launch_qkv_attention(EPI_BIAS_F16, U, d, L.wqkv.as<half_t>(), L.bqkv.as<float>(), nullptr,
-                                 cmask, ctx, nb, S, d, H, s, o8 ? ctx8 : nullptr);
-          else
-            launch_qkv_attention(EPI_LNF_F16, U, d, L.wqkv_f.as<half_t>(), L.dqkv.as<float>(), &lq,
-                                 cmask, ctx, nb, S, d, H, s, o8 ? ctx8 : nullptr);
-        } else if (l == 0) {
-          launch_gemm(EPI_BIAS_F16, U, d, L.wqkv.as<half_t>(), L.bqkv.as<float>(), nullptr, 0, qkv,
-                      3 * d, M, 3 * d, d, s);
-        } else if (qkv_8) {  // A = e4m3 copy of u (mode 2: by the previous FFN2) or of the
-                             // normalised rows (mode 4: quantize_norm_fp8, (mu, rstd) = (0, 1))
-          LnFold lq;
-          lq.mr = qkv_norm8 ? unit_mr_.as<float>() : mB;
-          lq.stat_ld = qkv_norm8 ? 0 : 1;
-          lq.colsum = L.cqkv8.as<float>();
-          lq.wexp = L.wqkve.as<uint8_t>();
-          launch_gemm_f8w(EPI_LNF_F16, u8, d, L.wqkv8.as<uint8_t>(), L.dqkv.as<float>(), nullptr, 0,
-                          qkv, 3 * d, M, 3 * d, d, s, &lq);
-        } else if (last && kvfree) {
-          // K/V-free CLS-only last layer: q of the CLS rows, w_h = W'_{k,h}^T q_h (one GEMM on the
-          // block-diagonal weight), scores / softmax / z' per sequence (as an fp16 hi + lo pair),
-          // ctx = W'_v z' + d_v (one GEMM, K = 2 H d)
-          LnFold lc;  // A = row b*S of each sequence (stride S*d), its statistics at row b*S
-          lc.mr = mB;
-          lc.stat_ld = S;
-          lc.colsum = L.cqkv.as<float>();
-          const int64_t HD = (int64_t)H * d;
-          half_t* qc = ffn;
-          half_t* wq = ffn + (int64_t)nb * d;
-          half_t* zq = wq + (int64_t)nb * HD;
-          launch_gemm(EPI_LNF_F16, U, (int64_t)S * d, L.wqkv_f.as<half_t>(), L.dqkv.as<float>(), nullptr,
-                      0, qc, d, nb, d, d, s, &lc);
-          launch_gemm(EPI_BIAS_F16, qc, d, L.wk_bd.as<half_t>(), L.zb.as<float>(), nullptr, 0, wq, HD, nb,
-                      (int)HD, d, s);
-          launch_cls_attn_fold(wq, U, mB, cmask, nb, S, d, H, zq, s);
-          launch_gemm(EPI_BIAS_F16, zq, 2 * HD, L.wv_bd.as<half_t>(), L.dqkv.as<float>() + 2 * d, nullptr,
-                      0, ctx, d, nb, d, (int)(2 * HD), s);
-        } else if (last && d % 256 == 0) {  // CLS-only last layer: K, V for all rows, Q for CLS rows
-          LnFold lq;
-          lq.mr = mB;
-          lq.colsum = L.cqkv.as<float>() + d;
-          launch_gemm(EPI_LNF_F16, U, d, L.wqkv_f.as<half_t>() + (int64_t)d * d, L.dqkv.as<float>() + d,
-                      nullptr, 0, qkv + d, 3 * d, M, 2 * d, d, s, &lq);
-          LnFold lc;  // A = row b*S of each sequence (stride S*d), its statistics at row b*S
-          lc.mr = mB;
-          lc.stat_ld = S;
-          lc.colsum = L.cqkv.as<float>();
-          launch_gemm(EPI_LNF_F16, U, (int64_t)S * d, L.wqkv_f.as<half_t>(), L.dqkv.as<float>(), nullptr,
-                      0, qkv, (int64_t)S * 3 * d, nb, d, d, s, &lc);
-        } else {  // A = u of the previous block, its LN2 folded into W'
-          LnFold lq;
-          lq.mr = mB;
-          lq.colsum = L.cqkv.as<float>();
-          launch_gemm(EPI_LNF_F16, U, d, L.wqkv_f.as<half_t>(), L.dqkv.as<float>(), nullptr, 0, qkv,
-                      3 * d, M, 3 * d, d, s, &lq);
-        }
-        const int Mr = last ? nb : M;
-        if (!(fuse_qa && !last) && !(last && kvfree))
-          launch_attention(qkv, cmask, ctx, nb, S, last ? 1 : S, d, H, s);
-        // O-projection + residual LN2(l-1)(u) -> u1 (in place, or compact rows) + partials sA
-        half_t* Uo = last ? Uc : U;
-        LnFold lo;
-        lo.mr = mB;
-        lo.stat_ld = last ? S : 1;
-        lo.gamma = P ? P->ln2g.as<float>() : nullptr;
-        lo.stat_out = sA;
-        lo.y8 = ffn1_8 ? u8 : nullptr;  // e4m3 copy of u1 for the fp8 FFN1
-        const int eo = ffn1_8 ? (l == 0 ? EPI_RES16_STATS_Y8 : EPI_LNR16_STATS_Y8)
-                                 : (l == 0 ? EPI_RES16_STATS : EPI_LNR16_STATS);
-        if (o8 && !last) {  // e4m3 ctx (K5c) x e4m3 W_o rows on the block-scaled fp8 MFMA
-          lo.wexp = L.woe.as<uint8_t>();
-          launch_gemm_f8w(eo, ctx8, d, L.wo_8.as<uint8_t>(), (l == 0 ? L.bo : L.bo_f).as<float>(), U,
-                          d, Uo, d, Mr, d, d, s, &lo);
-        } else {
-          launch_gemm(eo, ctx, d, L.wo.as<half_t>(),
-                      (l == 0 ? L.bo : L.bo_f).as<float>(), U, last ? (int64_t)S * d : d, Uo, d, Mr,
-                      d, d, s, &lo);
-        }
-        launch_ln_stats_finalize(sA, nparts, cfg_.ln_eps, Mr, mA, s);
-        // FFN1 on LN1(u1) folded; FFN2 + residual LN1(u1) -> u2 (in place) + partials sB
-        LnFold l1;
-        l1.mr = mA;
-        l1.colsum = L.c1.as<float>();
-        if (ffn1_8) {
-          l1.colsum = L.c1_8.as<float>();
-          l1.wexp = L.w1e.as<uint8_t>();
-          launch_gemm_f8w(EPI_LNF_GELU_F8, u8, d, L.w1_8.as<uint8_t>(), L.d1.as<float>(), nullptr, 0,
-                          ffn, F, Mr, F, d, s, &l1);
-        } else {
-          launch_gemm(fp8_ ? EPI_LNF_GELU_F8 : EPI_LNF_GELU_F16, Uo, d, L.w1_f.as<half_t>(),
-                      L.d1.as<float>(), nullptr, 0, ffn, F, Mr, F, d, s, &l1);
-        }
-        LnFold l2;
-        l2.mr = mA;
-        l2.gamma = L.ln1g.as<float>();
-        l2.stat_out = sB;
-        l2.wexp = L.w2e.as<uint8_t>();
-        l2.y8 = (qkv_8 && !qkv_norm8 && !last) ? u8 : nullptr;  // e4m3 copy of u2 for the next fp8 QKV
-        if (fp8_)  // ffn holds e4m3 bytes (F per row)
-          launch_gemm_f8w(l2.y8 ? EPI_LNR16_STATS_Y8 : EPI_LNR16_STATS, reinterpret_cast<const uint8_t*>(ffn), F,
-                          L.w2_8.as<uint8_t>(), L.b2_f.as<float>(), Uo, d, Uo, d, Mr, d, F, s, &l2);
-        else
-          launch_gemm(EPI_LNR16_STATS, ffn, F, L.w2h.as<half_t>(), L.b2_f.as<float>(), Uo, d, Uo,
-                      d, Mr, d, F, s, &l2);
-        launch_ln_stats_finalize(sB, nparts, cfg_.ln_eps, Mr, mB, s);
-        if (qkv_norm8 && l + 1 < layers_.size()) launch_quantize_norm_fp8(Uo, d, mB, Mr, d, u8, s);
-      }
-      // final LayerNorm (LN2 of the last block) of the rows that are consumed -> h16
-      const Layer& Lz = layers_.back();
-      launch_ln_apply(cls_only ? Uc : U, d, mB, Lz.ln2g.as<float>(), Lz.ln2b.as<float>(),
-                      cls_only ? nb : M, d, h16, s);
-    }
-    // split weights: W = [hi | lo] (N x 2K), the GEMM's K is 2K over the repeated activation
-    const int kr = split_ ? 2 : 1;
-    auto lin = [&](int epi, const half_t* X, int64_t lda, const half_t* W, const float* b,
-                   const void* R, int64_t ldr, void* Y, int64_t ldy, int Mm, int Nn, int Kx) {
-      LnFold lx;
-      lx.x_k = split_ ? Kx : 0;
-      lx.chunk_ws = chunk_ws_.as<float>();
-      lx.chunk_ws_bytes = (int64_t)chunk_ws_.bytes;
-      launch_gemm(epi, X, lda, W, b, R, ldr, Y, ldy, Mm, Nn, kr * Kx, s, &lx);
-    };
-    for (size_t l = 0; l < (fold ? 0 : layers_.size()); ++l) {
-      const Layer& L = layers_[l];
-      const bool last = cls_only && l + 1 == layers_.size();
-      lin(EPI_BIAS_F16, h16, d, L.wqkv.as<half_t>(), L.bqkv.as<float>(), nullptr, 0, qkv, 3 * d, M,
-          3 * d, d);
-      // rows of the rest of the block: all M tokens, or the nb CLS rows (compact) in the last layer
-      const int Mr = last ? nb : M;
-      launch_attention(qkv, cmask, ctx, nb, S, last ? 1 : S, d, H, s);
-      lin(epi_res, ctx, d, L.wo.as<half_t>(), L.bo.as<float>(), hres, last ? (int64_t)S * d : d, y,
-          d, Mr, d, d);
-      launch_layernorm(y, res16, L.ln1g.as<float>(), L.ln1b.as<float>(), cfg_.ln_eps, Mr, d, h16,
-                       h32w, s);
-      lin(EPI_BIAS_GELU_F16, h16, d, L.w1.as<half_t>(), L.b1.as<float>(), nullptr, 0, ffn, F, Mr, F,
-          d);
-      lin(epi_res, ffn, F, L.w2.as<half_t>(), L.b2.as<float>(), hres, d, y, d, Mr, d, F);
-      launch_layernorm(y, res16, L.ln2g.as<float>(), L.ln2b.as<float>(), cfg_.ln_eps, Mr, d, h16,
-                       h32w, s);
-    }
-    // final states: row b*S of each sequence, or row b (compact) after a CLS-only last layer
-    const int Sf = cls_only ? 1 : S;
-    if (mode == 0) {
-      const size_t esz = out_dtype == SR_DTYPE_F32 ? sizeof(float) : sizeof(half_t);
-      launch_pool_l2(res16 ? (const void*)h16 : (const void*)h32, res16, cmask, nb, Sf, d, pool,
-                     reinterpret_cast<char*>(out) + (size_t)b0 * ld_out * esz, out_dtype, ld_out, s);
-      if (sparse) {  // this chunk's token weights and terms, at the chunk's offset into B x S
-        float* tw = tok_weight + b0 * S;
-        launch_sparse_token_weights(res16 ? (const void*)h16 : (const void*)h32, res16, cmask,
-                                    sparse_w_.as<float>(), sparse_b_.as<float>(), M, d, tw, s);
-        launch_sparse_terms(cids, cmask, tw, nb, S, sparse->special_ids, sparse->n_special,
-                            sparse->terms + b0 * S, sparse->weights + b0 * S, sparse->count + b0, s);
-      }
-      if (mv) {  // v = W h + b for every token of the chunk (fp16), then normalise and compact
-        const int dc = colbert_dc_;
-        half_t* v = colbert_v_.as<half_t>();
-        launch_gemm(EPI_BIAS_F16, h16, d, colbert_w_.as<half_t>(), colbert_b_.as<float>(), nullptr, 0, v,
-                    dc, M, dc, d, s);
-        launch_colbert_pack(v, cmask, nb, S, dc, mv->vecs + b0 * S * dc, mv->len + b0, s);
-      }
-    } else {
-      float* t = clst_.as<float>();
-      launch_gemm(EPI_BIAS_TANH_F32, h16, (int64_t)Sf * d, wc_.as<half_t>(), bc_.as<float>(),
-                  nullptr, 0, t, d, nb, d, d, s);
-      launch_cls_logits(t, wout_.as<float>(), bout_.as<float>(), nb, d, cfg_.num_labels,
-                        reinterpret_cast<float*>(out) + b0 * cfg_.num_labels, s);
-    }
+    c.b0 = b0;
+    c.nb = (int)std::min<int64_t>(seqs_per_chunk, B - b0);
+    c.M = c.nb * S;
+    c.ids = ids + b0 * S;
+    c.mask = mask + b0 * S;
+    c.types = types ? types + b0 * S : nullptr;
+    embed_stage(c);
+    if (fold) folded_stack(c);
+    else unfolded_stack(c);
+    output_stage(c, mode, pool, out, out_dtype, ld_out, heads, tok_weight);
   }
   end(s);
 }
 
+void Encoder::embed_stage(const Chunk& c) {
+  int32_t* pos = pos_.as<int32_t>();
+  launch_positions(c.ids, pos, c.nb, c.S, cfg_.position_offset, c.s);
+  launch_embed_ln(c.ids, pos, c.types, wemb_.as<half_t>(), pemb_.as<half_t>(), temb_.as<half_t>(),
+                  embg_.as<float>(), embb_.as<float>(), cfg_.ln_eps, c.M, cfg_.hidden, cfg_.vocab_size,
+                  cfg_.max_position, cfg_.type_vocab, h16_.as<half_t>(),
+                  cfg_.residual_fp16 ? nullptr : h32_.as<float>(), c.s);
+}
+
+// The LN-folded layers (fp16 residual stream).  Per layer: QKV + attention -> ctx; O-projection +
+// residual -> u1 and its row statistics (sA -> mA); FFN1, FFN2 + residual -> u2 and its statistics
+// (sB -> mB).  In a CLS-only last layer the last two run on the nb CLS rows, compact in Uc.
+void Encoder::folded_stack(const Chunk& c) {
+  for (size_t l = 0; l < layers_.size(); ++l) {
+    const bool last = c.cls_only && l + 1 == layers_.size();
+    fold_qkv_attention(c, l, last);
+    fold_oproj(c, l, last);
+    fold_ffn(c, l, last);
+  }
+  // final LayerNorm (LN2 of the last block) of the rows that are consumed -> h16
+  const Layer& Lz = layers_.back();
+  launch_ln_apply(c.cls_only ? c.Uc : c.U, cfg_.hidden, c.mB, Lz.ln2g.as<float>(), Lz.ln2b.as<float>(),
+                  c.cls_only ? c.nb : c.M, cfg_.hidden, h16_.as<half_t>(), c.s);
+}
+
+// ctx of layer l from U, the previous block's u2 (layer 0: the embedding LayerNorm's output), with
+// that block's LN2 folded into W'qkv
+void Encoder::fold_qkv_attention(const Chunk& c, size_t l, bool last) {
+  const Layer& L = layers_[l];
+  const int d = cfg_.hidden, H = cfg_.heads, S = c.S, nb = c.nb, M = c.M;
+  half_t* U = c.U;
+  float* mB = c.mB;
+  half_t* qkv = qkv_.as<half_t>();
+  half_t* ctx = ctx_.as<half_t>();
+  hipStream_t s = c.s;
+  LnFold lq;  // A = u of the previous block, its LN2 folded into W'
+  lq.mr = mB;
+  lq.colsum = L.cqkv.as<float>();
+  LnFold lc = lq;  // A = row b*S of each sequence (stride S*d), its statistics at row b*S
+  lc.stat_ld = S;
+  if (c.fuse_qa && !last) {
+    if (l == 0)
+      launch_qkv_attention(EPI_BIAS_F16, U, d, L.wqkv.as<half_t>(), L.bqkv.as<float>(), nullptr,
+                           c.mask, ctx, nb, S, d, H, s, c.o8 ? c.ctx8 : nullptr);
+    else
+      launch_qkv_attention(EPI_LNF_F16, U, d, L.wqkv_f.as<half_t>(), L.dqkv.as<float>(), &lq,
+                           c.mask, ctx, nb, S, d, H, s, c.o8 ? c.ctx8 : nullptr);
+    return;  // K5c ran the attention too
+  }
+  if (l == 0) {
+    launch_gemm(EPI_BIAS_F16, U, d, L.wqkv.as<half_t>(), L.bqkv.as<float>(), nullptr, 0, qkv,
+                3 * d, M, 3 * d, d, s);
+  } else if (plan_.qkv) {  // A = e4m3 copy of u (by the previous FFN2) or, qkv_norm, of the
+                           // normalised rows (quantize_norm_fp8, (mu, rstd) = (0, 1))
+    LnFold l8;
+    l8.mr = plan_.qkv_norm ? unit_mr_.as<float>() : mB;
+    l8.stat_ld = plan_.qkv_norm ? 0 : 1;
+    l8.colsum = L.cqkv8.as<float>();
+    l8.wexp = L.wqkve.as<uint8_t>();
+    launch_gemm_f8w(EPI_LNF_F16, c.u8, d, L.wqkv8.as<uint8_t>(), L.dqkv.as<float>(), nullptr, 0,
+                    qkv, 3 * d, M, 3 * d, d, s, &l8);
+  } else if (last && c.kvfree) {
+    // K/V-free CLS-only last layer: q of the CLS rows, w_h = W'_{k,h}^T q_h (one GEMM on the
+    // block-diagonal weight), scores / softmax / z' per sequence (as an fp16 hi + lo pair),
+    // ctx = W'_v z' + d_v (one GEMM, K = 2 H d)
+    const int64_t HD = (int64_t)H * d;
+    half_t* qc = ffn_.as<half_t>();
+    half_t* wq = qc + (int64_t)nb * d;
+    half_t* zq = wq + (int64_t)nb * HD;
+    launch_gemm(EPI_LNF_F16, U, (int64_t)S * d, L.wqkv_f.as<half_t>(), L.dqkv.as<float>(), nullptr,
+                0, qc, d, nb, d, d, s, &lc);
+    launch_gemm(EPI_BIAS_F16, qc, d, L.wk_bd.as<half_t>(), L.zb.as<float>(), nullptr, 0, wq, HD, nb,
+                (int)HD, d, s);
+    launch_cls_attn_fold(wq, U, mB, c.mask, nb, S, d, H, zq, s);
+    launch_gemm(EPI_BIAS_F16, zq, 2 * HD, L.wv_bd.as<half_t>(), L.dqkv.as<float>() + 2 * d, nullptr,
+                0, ctx, d, nb, d, (int)(2 * HD), s);
+    return;  // ctx is written: no attention launch
+  } else if (last && d % 256 == 0) {  // CLS-only last layer: K, V for all rows, Q for CLS rows
+    LnFold lkv = lq;
+    lkv.colsum = L.cqkv.as<float>() + d;
+    launch_gemm(EPI_LNF_F16, U, d, L.wqkv_f.as<half_t>() + (int64_t)d * d, L.dqkv.as<float>() + d,
+                nullptr, 0, qkv + d, 3 * d, M, 2 * d, d, s, &lkv);
+    launch_gemm(EPI_LNF_F16, U, (int64_t)S * d, L.wqkv_f.as<half_t>(), L.dqkv.as<float>(), nullptr,
+                0, qkv, (int64_t)S * 3 * d, nb, d, d, s, &lc);
+  } else {
+    launch_gemm(EPI_LNF_F16, U, d, L.wqkv_f.as<half_t>(), L.dqkv.as<float>(), nullptr, 0, qkv,
+                3 * d, M, 3 * d, d, s, &lq);
+  }
+  launch_attention(qkv, c.mask, ctx, nb, S, last ? 1 : S, d, H, s);
+}
+
+// O-projection + residual LN2(l-1)(u) -> u1 (in place, or compact rows) + partials sA -> mA
+void Encoder::fold_oproj(const Chunk& c, size_t l, bool last) {
+  const Layer& L = layers_[l];
+  const Layer* P = l > 0 ? &layers_[l - 1] : nullptr;
+  const int d = cfg_.hidden, S = c.S;
+  const int Mr = last ? c.nb : c.M;
+  half_t* Uo = last ? c.Uc : c.U;
+  LnFold lo;
+  lo.mr = c.mB;
+  lo.stat_ld = last ? S : 1;
+  lo.gamma = P ? P->ln2g.as<float>() : nullptr;
+  lo.stat_out = c.sA;
+  lo.y8 = plan_.ffn1 ? c.u8 : nullptr;  // e4m3 copy of u1 for the fp8 FFN1
+  const int eo = plan_.ffn1 ? (l == 0 ? EPI_RES16_STATS_Y8 : EPI_LNR16_STATS_Y8)
+                            : (l == 0 ? EPI_RES16_STATS : EPI_LNR16_STATS);
+  if (c.o8 && !last) {  // e4m3 ctx (K5c) x e4m3 W_o rows on the block-scaled fp8 MFMA
+    lo.wexp = L.woe.as<uint8_t>();
+    launch_gemm_f8w(eo, c.ctx8, d, L.wo_8.as<uint8_t>(), (l == 0 ? L.bo : L.bo_f).as<float>(), c.U,
+                    d, Uo, d, Mr, d, d, c.s, &lo);
+  } else {
+    launch_gemm(eo, ctx_.as<half_t>(), d, L.wo.as<half_t>(),
+                (l == 0 ? L.bo : L.bo_f).as<float>(), c.U, last ? (int64_t)S * d : d, Uo, d, Mr,
+                d, d, c.s, &lo);
+  }
+  launch_ln_stats_finalize(c.sA, d / 128, cfg_.ln_eps, Mr, c.mA, c.s);
+}
+
+// FFN1 on LN1(u1) folded; FFN2 + residual LN1(u1) -> u2 (in place) + partials sB -> mB
+void Encoder::fold_ffn(const Chunk& c, size_t l, bool last) {
+  const Layer& L = layers_[l];
+  const int d = cfg_.hidden, F = cfg_.intermediate;
+  const int Mr = last ? c.nb : c.M;
+  half_t* Uo = last ? c.Uc : c.U;
+  half_t* ffn = ffn_.as<half_t>();
+  LnFold l1;
+  l1.mr = c.mA;
+  l1.colsum = L.c1.as<float>();
+  if (plan_.ffn1) {
+    l1.colsum = L.c1_8.as<float>();
+    l1.wexp = L.w1e.as<uint8_t>();
+    launch_gemm_f8w(EPI_LNF_GELU_F8, c.u8, d, L.w1_8.as<uint8_t>(), L.d1.as<float>(), nullptr, 0,
+                    ffn, F, Mr, F, d, c.s, &l1);
+  } else {
+    launch_gemm(plan_.ffn2 ? EPI_LNF_GELU_F8 : EPI_LNF_GELU_F16, Uo, d, L.w1_f.as<half_t>(),
+                L.d1.as<float>(), nullptr, 0, ffn, F, Mr, F, d, c.s, &l1);
+  }
+  LnFold l2;
+  l2.mr = c.mA;
+  l2.gamma = L.ln1g.as<float>();
+  l2.stat_out = c.sB;
+  l2.wexp = L.w2e.as<uint8_t>();
+  l2.y8 = (plan_.qkv && !plan_.qkv_norm && !last) ? c.u8 : nullptr;  // e4m3 copy of u2 for the next fp8 QKV
+  if (plan_.ffn2)  // ffn holds e4m3 bytes (F per row)
+    launch_gemm_f8w(l2.y8 ? EPI_LNR16_STATS_Y8 : EPI_LNR16_STATS, reinterpret_cast<const uint8_t*>(ffn), F,
+                    L.w2_8.as<uint8_t>(), L.b2_f.as<float>(), Uo, d, Uo, d, Mr, d, F, c.s, &l2);
+  else
+    launch_gemm(EPI_LNR16_STATS, ffn, F, L.w2h.as<half_t>(), L.b2_f.as<float>(), Uo, d, Uo,
+                d, Mr, d, F, c.s, &l2);
+  launch_ln_stats_finalize(c.sB, d / 128, cfg_.ln_eps, Mr, c.mB, c.s);
+  if (plan_.qkv_norm && l + 1 < layers_.size()) launch_quantize_norm_fp8(Uo, d, c.mB, Mr, d, c.u8, c.s);
+}
+
+// The layers with materialised LayerNorms (fp32 residual stream, or SR_LN_FOLD=0)
+void Encoder::unfolded_stack(const Chunk& c) {
+  const int d = cfg_.hidden, F = cfg_.intermediate, H = cfg_.heads, S = c.S, nb = c.nb, M = c.M;
+  half_t* h16 = h16_.as<half_t>();
+  half_t* qkv = qkv_.as<half_t>();
+  half_t* ctx = ctx_.as<half_t>();
+  half_t* ffn = ffn_.as<half_t>();
+  void* y = y32_.p;  // bias + residual sum: fp32, or fp16 with an fp16 residual stream
+  const bool res16 = cfg_.residual_fp16 != 0;
+  const void* hres = res16 ? (const void*)h16 : (const void*)h32_.p;  // residual operand
+  float* h32w = res16 ? nullptr : h32_.as<float>();
+  const int epi_res = res16 ? EPI_BIAS_RES_F16 : EPI_BIAS_RES_F32;
+  // split weights: W = [hi | lo] (N x 2K), the GEMM's K is 2K over the repeated activation
+  const int kr = split_ ? 2 : 1;
+  auto lin = [&](int epi, const half_t* X, int64_t lda, const half_t* W, const float* b,
+                 const void* R, int64_t ldr, void* Y, int64_t ldy, int Mm, int Nn, int Kx) {
+    LnFold lx;
+    lx.x_k = split_ ? Kx : 0;
+    lx.chunk_ws = chunk_ws_.as<float>();
+    lx.chunk_ws_bytes = (int64_t)chunk_ws_.bytes;
+    launch_gemm(epi, X, lda, W, b, R, ldr, Y, ldy, Mm, Nn, kr * Kx, c.s, &lx);
+  };
+  for (size_t l = 0; l < layers_.size(); ++l) {
+    const Layer& L = layers_[l];
+    const bool last = c.cls_only && l + 1 == layers_.size();
+    lin(EPI_BIAS_F16, h16, d, L.wqkv.as<half_t>(), L.bqkv.as<float>(), nullptr, 0, qkv, 3 * d, M,
+        3 * d, d);
+    // rows of the rest of the block: all M tokens, or the nb CLS rows (compact) in the last layer
+    const int Mr = last ? nb : M;
+    launch_attention(qkv, c.mask, ctx, nb, S, last ? 1 : S, d, H, c.s);
+    lin(epi_res, ctx, d, L.wo.as<half_t>(), L.bo.as<float>(), hres, last ? (int64_t)S * d : d, y,
+        d, Mr, d, d);
+    launch_layernorm(y, res16, L.ln1g.as<float>(), L.ln1b.as<float>(), cfg_.ln_eps, Mr, d, h16,
+                     h32w, c.s);
+    lin(EPI_BIAS_GELU_F16, h16, d, L.w1.as<half_t>(), L.b1.as<float>(), nullptr, 0, ffn, F, Mr, F,
+        d);
+    lin(epi_res, ffn, F, L.w2.as<half_t>(), L.b2.as<float>(), hres, d, y, d, Mr, d, F);
+    launch_layernorm(y, res16, L.ln2g.as<float>(), L.ln2b.as<float>(), cfg_.ln_eps, Mr, d, h16,
+                     h32w, c.s);
+  }
+}
+
+// Pooled embeddings (+ the token heads) or classifier logits of the chunk, from the final states:
+// row b*S of each sequence, or row b (compact) after a CLS-only last layer
+void Encoder::output_stage(const Chunk& c, int mode, int pool, void* out, int out_dtype, int ld_out,
+                           const TokenHeads* heads, float* tok_weight) {
+  const int d = cfg_.hidden, S = c.S, nb = c.nb, M = c.M;
+  const int64_t b0 = c.b0;
+  half_t* h16 = h16_.as<half_t>();
+  const bool res16 = cfg_.residual_fp16 != 0;
+  const void* hfin = res16 ? (const void*)h16 : (const void*)h32_.p;
+  const int Sf = c.cls_only ? 1 : S;
+  if (mode == 1) {
+    float* t = clst_.as<float>();
+    launch_gemm(EPI_BIAS_TANH_F32, h16, (int64_t)Sf * d, wc_.as<half_t>(), bc_.as<float>(),
+                nullptr, 0, t, d, nb, d, d, c.s);
+    launch_cls_logits(t, wout_.as<float>(), bout_.as<float>(), nb, d, cfg_.num_labels,
+                      reinterpret_cast<float*>(out) + b0 * cfg_.num_labels, c.s);
+    return;
+  }
+  const size_t esz = out_dtype == SR_DTYPE_F32 ? sizeof(float) : sizeof(half_t);
+  launch_pool_l2(hfin, res16, c.mask, nb, Sf, d, pool,
+                 reinterpret_cast<char*>(out) + (size_t)b0 * ld_out * esz, out_dtype, ld_out, c.s);
+  if (heads && heads->sparse) {  // this chunk's token weights and terms, at the chunk's offset into B x S
+    const SparseOut* sparse = heads->sparse;
+    float* tw = tok_weight + b0 * S;
+    launch_sparse_token_weights(hfin, res16, c.mask, sparse_w_.as<float>(), sparse_b_.as<float>(), M, d,
+                                tw, c.s);
+    launch_sparse_terms(c.ids, c.mask, tw, nb, S, sparse->special_ids, sparse->n_special,
+                        sparse->terms + b0 * S, sparse->weights + b0 * S, sparse->count + b0, c.s);
+  }
+  if (heads && heads->multivec) {  // v = W h + b for every token of the chunk (fp16), then normalise and compact
+    const MultiVecOut* mv = heads->multivec;
+    const int dc = colbert_dc_;
+    half_t* v = colbert_v_.as<half_t>();
+    launch_gemm(EPI_BIAS_F16, h16, d, colbert_w_.as<half_t>(), colbert_b_.as<float>(), nullptr, 0, v,
+                dc, M, dc, d, c.s);
+    launch_colbert_pack(v, c.mask, nb, S, dc, mv->vecs + b0 * S * dc, mv->len + b0, c.s);
+  }
+}
+
 void Encoder::forward_host(const int32_t* ids, const int32_t* mask, const int32_t* types, int B,
-                           int S, int mode, int pool, float* out) {
-  SR_CHECK(B >= 0 && S >= 1 && (B == 0 || (ids && mask && out)), "encoder: null buffer");
+                           int S, int mode, int pool, float* out, const SparseOut* sparse,
+                           const MultiVecHost* mv) {
+  SR_CHECK(B >= 0 && S >= 1, "encoder: bad batch shape");
+  SR_CHECK(B == 0 || (ids && mask && out && (!mv || (mv->vecs && mv->len)) &&
+                      (!sparse || (sparse->terms && sparse->weights && sparse->count))),
+           "encoder: null buffer");
+  if (sparse) sparse_terms_check_args(B, S, sparse->n_special);
+  if (mv) {  // the head's width sizes the staging
+    if (!(colbert_w_set_ && colbert_b_set_))
+      throw Error(SR_ERR_STATE, std::string("encoder: weight not set: colbert_linear.") +
+                                    (colbert_w_set_ ? "bias" : "weight"));
+    colbert_pack_check_args(B, S, colbert_dc_);
+  }
   if (B == 0) return;
   DeviceGuard g(device_);
-  const int64_t n = (int64_t)B * S;
-  const int64_t out_elems = (int64_t)B * (mode == 0 ? cfg_.hidden : cfg_.num_labels);
+  const size_t n = (size_t)B * S, nv = mv ? n * colbert_dc_ : 0;
+  const size_t out_elems = (size_t)B * (mode == 0 ? cfg_.hidden : cfg_.num_labels);
   int32_t *dids, *dmask, *dtypes = nullptr;
   float* dout;
-  Carve c;
-  c.part((size_t)n, &dids, &dmask);
-  if (types) c.part((size_t)n, &dtypes);
-  c.part((size_t)out_elems, &dout);
-  hostio_.carve(c);
-  SR_HIP(hipMemcpyAsync(dids, ids, n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-  SR_HIP(hipMemcpyAsync(dmask, mask, n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-  if (types) SR_HIP(hipMemcpyAsync(dtypes, types, n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-  forward_dev(dids, dmask, dtypes, B, S, mode, pool, dout, SR_DTYPE_F32, cfg_.hidden, stream_);
-  SR_HIP(hipMemcpyAsync(out, dout, (size_t)out_elems * sizeof(float), hipMemcpyDeviceToHost, stream_));
-  SR_HIP(hipStreamSynchronize(stream_));
-}
-
-void Encoder::forward_sparse_host(const int32_t* ids, const int32_t* mask, const int32_t* types,
-                                  int B, int S, int pool, float* out_dense, const int32_t* special_ids,
-                                  int n_special, float* out_tok_weight, int32_t* out_terms,
-                                  float* out_weights, int32_t* out_count) {
-  SR_CHECK(B >= 0 && S >= 1, "encoder: bad batch shape");
-  SR_CHECK(B == 0 || (ids && mask && out_dense && out_terms && out_weights && out_count),
-           "encoder: null buffer");
-  sparse_terms_check_args(B, S, n_special);
-  if (B == 0) return;
-  DeviceGuard g(device_);
-  const size_t n = (size_t)B * S;
-  int32_t *dids, *dmask, *dtypes = nullptr, *dterms, *dcount;
-  float *dout, *dtw, *dw;
+  SparseOut so{};
+  MultiVecOut mo{};
   Carve c;
   c.part(n, &dids, &dmask);
   if (types) c.part(n, &dtypes);
-  c.part((size_t)B * cfg_.hidden, &dout);
-  c.part(n, &dtw, &dterms, &dw);
-  c.part((size_t)B, &dcount);
-  hostio_.carve(c);
-  SR_HIP(hipMemcpyAsync(dids, ids, n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-  SR_HIP(hipMemcpyAsync(dmask, mask, n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-  if (types) SR_HIP(hipMemcpyAsync(dtypes, types, n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-  const SparseOut so{special_ids, n_special, dtw, dterms, dw, dcount};
-  TokenHeads th;
-  th.sparse = &so;
-  forward_dev(dids, dmask, dtypes, B, S, 0, pool, dout, SR_DTYPE_F32, cfg_.hidden, stream_, &th);
-  SR_HIP(hipMemcpyAsync(out_dense, dout, (size_t)B * cfg_.hidden * sizeof(float), hipMemcpyDeviceToHost, stream_));
-  if (out_tok_weight) SR_HIP(hipMemcpyAsync(out_tok_weight, dtw, n * sizeof(float), hipMemcpyDeviceToHost, stream_));
-  SR_HIP(hipMemcpyAsync(out_terms, dterms, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
-  SR_HIP(hipMemcpyAsync(out_weights, dw, n * sizeof(float), hipMemcpyDeviceToHost, stream_));
-  SR_HIP(hipMemcpyAsync(out_count, dcount, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
-  SR_HIP(hipStreamSynchronize(stream_));
-}
-
-void Encoder::forward_multivec_host(const int32_t* ids, const int32_t* mask, const int32_t* types,
-                                    int B, int S, int pool, float* out_dense, float* out_vecs,
-                                    int32_t* out_len, const int32_t* special_ids, int n_special,
-                                    float* out_tok_weight, int32_t* out_terms, float* out_weights,
-                                    int32_t* out_count) {
-  SR_CHECK(B >= 0 && S >= 1, "encoder: bad batch shape");
-  const bool any_sparse = out_tok_weight || out_terms || out_weights || out_count;
-  const bool with_sparse = out_terms && out_weights && out_count;
-  SR_CHECK(!any_sparse || with_sparse,
-           "encoder: the sparse outputs are one group: terms, weights and count together or none");
-  SR_CHECK(B == 0 || (ids && mask && out_dense && out_vecs && out_len), "encoder: null buffer");
-  if (with_sparse) sparse_terms_check_args(B, S, n_special);
-  if (!(colbert_w_set_ && colbert_b_set_))
-    throw Error(SR_ERR_STATE, std::string("encoder: weight not set: colbert_linear.") +
-                                  (colbert_w_set_ ? "bias" : "weight"));
-  colbert_pack_check_args(B, S, colbert_dc_);
-  if (B == 0) return;
-  DeviceGuard g(device_);
-  const size_t n = (size_t)B * S, nv = n * colbert_dc_;
-  int32_t *dids, *dmask, *dtypes = nullptr, *dlen, *dterms = nullptr, *dcount = nullptr;
-  float *dout, *dtw = nullptr, *dw = nullptr;
-  half_t* dvecs;
-  Carve c;
-  c.part(n, &dids, &dmask);
-  if (types) c.part(n, &dtypes);
-  c.part((size_t)B * cfg_.hidden, &dout);
-  c.part(nv, &dvecs);
-  c.part((size_t)B, &dlen);
-  if (with_sparse) {
-    c.part(n, &dtw, &dterms, &dw);
-    c.part((size_t)B, &dcount);
+  c.part(out_elems, &dout);
+  if (sparse) {
+    so.special_ids = sparse->special_ids;
+    so.n_special = sparse->n_special;
+    c.part(n, &so.tok_weight, &so.terms, &so.weights);
+    c.part((size_t)B, &so.count);
+  }
+  if (mv) {
+    c.part(nv, &mo.vecs);
+    c.part((size_t)B, &mo.len);
   }
   hostio_.carve(c);
-  SR_HIP(hipMemcpyAsync(dids, ids, n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-  SR_HIP(hipMemcpyAsync(dmask, mask, n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-  if (types) SR_HIP(hipMemcpyAsync(dtypes, types, n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-  const SparseOut so{special_ids, n_special, dtw, dterms, dw, dcount};
-  const MultiVecOut mo{dvecs, dlen};
+  auto up = [&](int32_t* dst, const int32_t* src) {
+    SR_HIP(hipMemcpyAsync(dst, src, n * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+  };
+  auto down = [&](void* dst, const void* src, size_t bytes) {
+    SR_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream_));
+  };
+  up(dids, ids);
+  up(dmask, mask);
+  if (types) up(dtypes, types);
   TokenHeads th;
-  th.sparse = with_sparse ? &so : nullptr;
-  th.multivec = &mo;
-  forward_dev(dids, dmask, dtypes, B, S, 0, pool, dout, SR_DTYPE_F32, cfg_.hidden, stream_, &th);
-  std::vector<half_t> hv(nv);
-  SR_HIP(hipMemcpyAsync(out_dense, dout, (size_t)B * cfg_.hidden * sizeof(float), hipMemcpyDeviceToHost, stream_));
-  SR_HIP(hipMemcpyAsync(hv.data(), dvecs, nv * sizeof(half_t), hipMemcpyDeviceToHost, stream_));
-  SR_HIP(hipMemcpyAsync(out_len, dlen, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
-  if (with_sparse) {
-    if (out_tok_weight) SR_HIP(hipMemcpyAsync(out_tok_weight, dtw, n * sizeof(float), hipMemcpyDeviceToHost, stream_));
-    SR_HIP(hipMemcpyAsync(out_terms, dterms, n * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
-    SR_HIP(hipMemcpyAsync(out_weights, dw, n * sizeof(float), hipMemcpyDeviceToHost, stream_));
-    SR_HIP(hipMemcpyAsync(out_count, dcount, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+  th.sparse = sparse ? &so : nullptr;
+  th.multivec = mv ? &mo : nullptr;
+  forward_dev(dids, dmask, dtypes, B, S, mode, pool, dout, SR_DTYPE_F32, cfg_.hidden, stream_,
+              sparse || mv ? &th : nullptr);
+  std::vector<half_t> hv(nv);  // the multi-vector output is fp16 on the device, fp32 for the caller
+  down(out, dout, out_elems * sizeof(float));
+  if (mv) {
+    down(hv.data(), mo.vecs, nv * sizeof(half_t));
+    down(mv->len, mo.len, (size_t)B * sizeof(int32_t));
+  }
+  if (sparse) {
+    if (sparse->tok_weight) down(sparse->tok_weight, so.tok_weight, n * sizeof(float));
+    down(sparse->terms, so.terms, n * sizeof(int32_t));
+    down(sparse->weights, so.weights, n * sizeof(float));
+    down(sparse->count, so.count, (size_t)B * sizeof(int32_t));
   }
   SR_HIP(hipStreamSynchronize(stream_));
-  for (size_t i = 0; i < nv; ++i) out_vecs[i] = (float)hv[i];
+  for (size_t i = 0; i < nv; ++i) mv->vecs[i] = (float)hv[i];
 }
 
 }  // namespace sr

@@ -249,25 +249,29 @@ class Encoder {
   void forward_dev(const int32_t* ids, const int32_t* mask, const int32_t* types, int B, int S,
                    int mode, int pool, void* out, int out_dtype, int ld_out, hipStream_t s,
                    const TokenHeads* heads = nullptr);
-  // host buffers, blocking: the dense embedding, the multi-vector (fp16 values as fp32, B x S x dc)
-  // and, with out_terms set, the sparse outputs of forward_sparse_host
-  void forward_multivec_host(const int32_t* ids, const int32_t* mask, const int32_t* types, int B, int S,
-                             int pool, float* out_dense, float* out_vecs, int32_t* out_len,
-                             const int32_t* special_ids, int n_special, float* out_tok_weight,
-                             int32_t* out_terms, float* out_weights, int32_t* out_count);
-  int colbert_dim() const { return colbert_w_set_ ? colbert_dc_ : 0; }
-  // host buffers, blocking: the dense embedding (fp32 B x hidden) and the sparse outputs
-  void forward_sparse_host(const int32_t* ids, const int32_t* mask, const int32_t* types, int B, int S,
-                           int pool, float* out_dense, const int32_t* special_ids, int n_special,
-                           float* out_tok_weight, int32_t* out_terms, float* out_weights,
-                           int32_t* out_count);
+  // the multi-vector group of forward_host: the fp16 values as fp32, B x S x dc, and the counts
+  struct MultiVecHost {
+    float* vecs;
+    int32_t* len;
+  };
+  // host buffers, blocking: upload, forward_dev, download.  `out` is the dense embedding (mode 0,
+  // fp32 B x hidden) or the logits (mode 1); the optional groups (mode 0) are the sparse outputs
+  // (a SparseOut of host pointers) and the multi-vector outputs
   void forward_host(const int32_t* ids, const int32_t* mask, const int32_t* types, int B, int S,
-                    int mode, int pool, float* out);
+                    int mode, int pool, float* out, const SparseOut* sparse = nullptr,
+                    const MultiVecHost* multivec = nullptr);
+  int colbert_dim() const { return colbert_w_set_ ? colbert_dc_ : 0; }
 
   const sr_encoder_config& config() const { return cfg_; }
-  // fp8 modes (LN-folded encoders): 1 = FFN (FFN1 stores e4m3(2 GELU), FFN2 on the block-scaled
-  // fp8 MFMA with an e4m3 copy of its weight); 2 = also FFN1 and the QKV GEMMs of layers >= 1 on
-  // e4m3 copies of the residual sums written by the *_STATS epilogues; 0 = fp16
+  // fp8 modes (LN-folded encoders), 0 = fp16.  Product modes: 1 = FFN2 (FFN1 stores e4m3(2 GELU),
+  // FFN2 runs on the block-scaled fp8 MFMA with an e4m3 copy of its weight); 3 = FFN1 + FFN2 (FFN1
+  // reads the e4m3 copy of the residual sums that the O-projection's *_STATS epilogue writes; QKV +
+  // attention stay fp16, fused): the shipped fp8 mode, it ranks like the fp32 oracle on the
+  // discriminative fidelity sets; 2 = mode 3 + the QKV GEMMs of layers >= 1 on the e4m3 residual
+  // copy, an opt-in speed / fidelity trade (std / err 2.0).  Measured and rejected (the
+  // diagnostic library keeps them for the record): 4 = mode 3 + QKV in fp8 on normalised e4m3 rows
+  // (2.0), 5 = mode 3 + the O-projection of the fused layers on e4m3 ctx written by K5c (6.4).
+  // fp8_plan() is the only code that knows the numbers.
   void set_fp8(int mode);
   int device() const { return device_; }
   std::mutex mu;
@@ -291,13 +295,48 @@ class Encoder {
     // K/V-free CLS-only last layer: block-diagonal K / V weights, zero bias (H*D)
     DevBuf wk_bd, wv_bd, zb;
   };
+  // which GEMMs of the folded layers an fp8 mode runs on the block-scaled fp8 MFMA
+  struct Fp8Plan {
+    bool ffn2 = false;      // FFN2 on e4m3(2 GELU) written by FFN1
+    bool ffn1 = false;      // FFN1 on the e4m3 copy of u1 written by the O-projection
+    bool qkv = false;       // QKV of layers >= 1 on an e4m3 copy of the previous block's output
+    bool qkv_norm = false;  // ... of its NORMALISED rows (quantize_norm_fp8), not of u2 itself
+    bool oproj = false;     // O-projection of the fused layers on e4m3 ctx written by K5c
+  };
+  static Fp8Plan fp8_plan(int mode);
+  // one launch chunk of forward_dev: nb sequences, M = nb * S tokens, from sequence b0 on
+  struct Chunk {
+    int64_t b0;
+    int nb, S, M;
+    const int32_t *ids, *mask, *types;  // at the chunk's first token (types may be null)
+    bool cls_only;                      // only the first token's final state is consumed
+    hipStream_t s;
+    // the folded stack: u (un-normalised residual sums) lives in h16 (in place), the compact
+    // last-layer rows in y32_; sA / mA: statistics of u after the O-projection, sB / mB: after FFN2
+    half_t *U, *Uc;
+    float *sA, *sB, *mA, *mB;
+    uint8_t *u8, *ctx8;                 // e4m3 copies: residual rows; the fused layers' ctx (mode 5)
+    bool fuse_qa, o8, kvfree;           // K5c layers; their fp8 O-projection; K/V-free last layer
+  };
   bool fold_enabled() const;
   void prepare_fold(hipStream_t s);
   void begin(hipStream_t s) { SR_HIP(hipStreamWaitEvent(s, done_, 0)); }
   void end(hipStream_t s) { SR_HIP(hipEventRecord(done_, s)); }
   void register_target(const std::string& name, DevBuf& buf, int64_t numel, bool f16,
                        int64_t offset_elems = 0, int64_t total_elems = -1, int64_t split_k = 0);
-  void ensure_ws(int64_t tokens, int B);
+  void ensure_ws(int64_t tokens);
+  // forward_dev's stages, in call order
+  void check_forward(int B, int S, int mode, int pool, int out_dtype, int ld_out,
+                     const TokenHeads* heads) const;
+  float* reserve_forward(int B, int S, int mode, int64_t chunk_seqs, const TokenHeads* heads);
+  void embed_stage(const Chunk& c);
+  void folded_stack(const Chunk& c);
+  void fold_qkv_attention(const Chunk& c, size_t l, bool last);
+  void fold_oproj(const Chunk& c, size_t l, bool last);
+  void fold_ffn(const Chunk& c, size_t l, bool last);
+  void unfolded_stack(const Chunk& c);
+  void output_stage(const Chunk& c, int mode, int pool, void* out, int out_dtype, int ld_out,
+                    const TokenHeads* heads, float* tok_weight);
 
   sr_encoder_config cfg_;
   int device_;
@@ -321,7 +360,8 @@ class Encoder {
   int colbert_dc_ = 0;
   DevBuf statA_, statB_, mrA_, mrB_;  // per-row LayerNorm partials / (mu, rstd) (folded path)
   bool fold_ready_ = false;  // folded weights match the current weights
-  int fp8_ = 0;
+  int fp8_ = 0;      // the mode set_fp8 was given
+  Fp8Plan plan_;     // = fp8_plan(fp8_): what prepare_fold and the folded stages read
   // split weights (fp32-residual encoders, i.e. the embedders): each layer matrix W is held as
   // [fp16(W) | fp16(W - fp16(W))] and the GEMMs run K = 2 K_x over the repeated activation, which
   // removes the fp16 weight rounding (~9e-4 of the 1.1e-3 embedding error of 24-layer bge-m3)
