@@ -3,7 +3,8 @@
  * Exported by libsrmi_diag.so only (make -C super-rag_amd: the product sources built again with
  * SR_WITH_DIAG=1), never by the product library libsrmi.so.  These entry points drive ONE kernel
  * on device buffers for single-kernel parity tests (tests/test_gpu_gemm.py, test_gpu_attention.py,
- * test_gpu_ffn1_epilogue.py), microbenchmarks (tools/) and the measured peaks of bench.py; the
+ * test_gpu_ffn1_epilogue.py, test_gpu_ffn1_gelu_sweep.py, test_gpu_gemm_f8_fold.py,
+ * test_gpu_fold_helpers.py), microbenchmarks (tools/) and the measured peaks of bench.py; the
  * timing-only variants return wrong results by design.  The diagnostic library also honours the
  * A/B environment knobs of DESIGN.md §4 (SR_GEMM_GROUP_M, SR_GEMM_STAGGER, SR_SCAN_CHUNK,
  * SR_SCAN_GROWTH, SR_SCAN_LEGACY, SR_SCAN_DIAG_NOEPI, SR_QA_DIAG, SR_FFN1_DIAG_WALKERS), which the
@@ -81,6 +82,38 @@ int sr_diag_gemm_stats_y8(int lnr, const void* X, int64_t lda, const void* W, co
                           const void* R, int64_t ldr, const float* mr, const float* gamma, void* Y,
                           int64_t ldy, uint8_t* y8, int M, int N, int K, float* stat_out, int device,
                           void* stream);
+
+/* Diagnostic: one LayerNorm-folded encoder GEMM the way the product launches it (launch_gemm /
+ * launch_gemm_f8w with the automatic kernel choice, no forced variant), every LnFold field and row
+ * stride from the arguments.  f8 = 0: X M x K, W N x K fp16; f8 = 1: X, W OCP e4m3 bytes (K % 128
+ * == 0, K >= 256) and wexp the E8M0 exponent byte of each W row (W = W8 2^(wexp - 127)).  epi (the
+ * Epilogue codes): 5 EPI_LNF_F16 Y = rstd_m (X W^T - mu_m colsum) + bias; 7 EPI_RES16_STATS Y =
+ * X W^T + bias + R; 8 EPI_LNR16_STATS Y = X W^T + bias + ((R - mu_m) rstd_m) gamma; 12 / 13 = 7 / 8
+ * that also store e4m3(Y) bytes to y8 (row stride ldy).  (mu_m, rstd_m) = mr[2 m stat_ld + {0, 1}]
+ * (row m of the operand reads statistics row m x stat_ld); R / Y fp16 with row strides ldr / ldy
+ * (Y may alias R); stat_out [M][N / 128][2] the (sum, M2) partials of the fp16 Y (epi 7, 8, 12,
+ * 13).  Buffers an epilogue does not read may be null.  N % 256 == 0, M > 0. */
+int sr_diag_gemm_fold(int f8, int epi, const void* X, int64_t lda, const void* W, const uint8_t* wexp,
+                      const float* bias, const float* colsum, const void* R, int64_t ldr, const float* mr,
+                      int64_t stat_ld, const float* gamma, void* Y, int64_t ldy, uint8_t* y8,
+                      float* stat_out, int M, int N, int K, int device, void* stream);
+
+/* Diagnostic: the weight-side helpers of the LayerNorm fold and the fp8 plan, one kernel each on
+ * device buffers.  quantize_rows_fp8: W N x K fp16 -> W8 e4m3(W 2^e_n) bytes with e_n the largest
+ * power of two keeping max|W_n| 2^e_n <= 448 (0 for a zero row), wexp[n] = 127 - e_n.  colsum_fp8:
+ * colsum[n] = sum_k W8[n][k] 2^(wexp[n] - 127).  fold_ln_weight: w16 = fp16(w32 . diag(gamma)),
+ * colsum[n] = sum_k float(w16[n][k]), bias_out[n] = sum_k w32[n][k] beta[k] + bias[n].
+ * ln_stats_finalize: mr[m] = (mu, rstd = 1 / sqrt(var + eps)) of row m from its nparts (1..16)
+ * (sum, M2) partials over 128-column spans, stat [M][nparts][2]. */
+int sr_diag_quantize_rows_fp8(const void* W, int N, int K, uint8_t* W8, uint8_t* wexp, int device,
+                              void* stream);
+int sr_diag_colsum_fp8(const uint8_t* W8, const uint8_t* wexp, int N, int K, float* colsum, int device,
+                       void* stream);
+int sr_diag_fold_ln_weight(const float* w32, const float* gamma, const float* beta, const float* bias,
+                           int N, int K, void* w16, float* colsum, float* bias_out, int device,
+                           void* stream);
+int sr_diag_ln_stats_finalize(const float* stat, int nparts, float eps, int M, float* mr, int device,
+                              void* stream);
 
 /* Diagnostic: the MFMA issue-rate peak on this box (k_diag.hip).  blocks workgroups of 8 waves,
  * each wave 8 independent accumulator chains x iters of the product's MFMA (f8 = 0: f16

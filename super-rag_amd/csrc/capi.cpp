@@ -1538,6 +1538,109 @@ int sr_diag_gemm_stats_y8(int lnr, const void* X, int64_t lda, const void* W, co
   SR_API_END
 }
 
+int sr_diag_gemm_fold(int f8, int epi, const void* X, int64_t lda, const void* W, const uint8_t* wexp,
+                      const float* bias, const float* colsum, const void* R, int64_t ldr, const float* mr,
+                      int64_t stat_ld, const float* gamma, void* Y, int64_t ldy, uint8_t* y8,
+                      float* stat_out, int M, int N, int K, int device, void* stream) {
+  SR_API_BEGIN
+  const bool lnf = epi == sr::EPI_LNF_F16;
+  const bool lnr = epi == sr::EPI_LNR16_STATS || epi == sr::EPI_LNR16_STATS_Y8;
+  const bool with_y8 = epi == sr::EPI_RES16_STATS_Y8 || epi == sr::EPI_LNR16_STATS_Y8;
+  const bool stats = lnr || epi == sr::EPI_RES16_STATS || epi == sr::EPI_RES16_STATS_Y8;
+  SR_CHECK(lnf || stats, "diag_gemm_fold: epi must be LNF_F16 (5), RES16_STATS (7), LNR16_STATS (8) or "
+                         "their e4m3-copy forms (12, 13)");
+  SR_NONNULL(X);
+  SR_NONNULL(W);
+  SR_NONNULL(bias);
+  SR_NONNULL(Y);
+  SR_CHECK(M > 0 && N > 0 && N % 256 == 0, "diag_gemm_fold: M > 0, N a positive multiple of 256");
+  SR_CHECK(!f8 || wexp, "diag_gemm_fold: fp8 needs wexp");
+  SR_CHECK(f8 ? (K % 128 == 0 && K >= 256) : (K % 64 == 0 && K >= 64),
+           "diag_gemm_fold: K % 128 == 0, K >= 256 (fp8) / K % 64 == 0 (fp16)");
+  SR_CHECK(lda >= K && lda % (f8 ? 16 : 8) == 0, "diag_gemm_fold: lda >= K, 16-byte rows");
+  SR_CHECK(ldy >= N && ldy % 8 == 0, "diag_gemm_fold: ldy >= N, ldy % 8 == 0");
+  SR_CHECK(!stats || (R && ldr >= N && ldr % 8 == 0), "diag_gemm_fold: the residual epilogues need R, ldr >= N, ldr % 8 == 0");
+  SR_CHECK(!(lnf || lnr) || (mr && stat_ld >= 0), "diag_gemm_fold: LN-folded epilogues need mr, stat_ld >= 0");
+  SR_CHECK(!lnf || colsum, "diag_gemm_fold: LNF needs colsum");
+  SR_CHECK(!lnr || gamma, "diag_gemm_fold: LNR needs gamma");
+  SR_CHECK(!stats || stat_out, "diag_gemm_fold: the *_STATS epilogues need stat_out");
+  SR_CHECK(!with_y8 || y8, "diag_gemm_fold: the e4m3-copy epilogues need y8");
+  sr::DeviceGuard g(device);
+  sr::LnFold lf;
+  lf.mr = (lnf || lnr) ? mr : nullptr;
+  lf.stat_ld = (lnf || lnr) ? stat_ld : 1;
+  lf.colsum = lnf ? colsum : nullptr;
+  lf.gamma = lnr ? gamma : nullptr;
+  lf.stat_out = stats ? stat_out : nullptr;
+  lf.y8 = with_y8 ? y8 : nullptr;
+  lf.wexp = f8 ? wexp : nullptr;
+  if (f8)
+    sr::launch_gemm_f8w(epi, reinterpret_cast<const uint8_t*>(X), lda, reinterpret_cast<const uint8_t*>(W), bias,
+                        stats ? R : nullptr, stats ? ldr : 0, Y, ldy, M, N, K,
+                        reinterpret_cast<hipStream_t>(stream), &lf);
+  else
+    sr::launch_gemm(epi, reinterpret_cast<const sr::half_t*>(X), lda, reinterpret_cast<const sr::half_t*>(W),
+                    bias, stats ? R : nullptr, stats ? ldr : 0, Y, ldy, M, N, K,
+                    reinterpret_cast<hipStream_t>(stream), &lf);
+  SR_API_END
+}
+
+int sr_diag_quantize_rows_fp8(const void* W, int N, int K, uint8_t* W8, uint8_t* wexp, int device,
+                              void* stream) {
+  SR_API_BEGIN
+  SR_NONNULL(W);
+  SR_NONNULL(W8);
+  SR_NONNULL(wexp);
+  SR_CHECK(N > 0 && K > 0, "diag_quantize_rows_fp8: N > 0, K > 0");
+  sr::DeviceGuard g(device);
+  sr::launch_quantize_rows_fp8(reinterpret_cast<const sr::half_t*>(W), N, K, W8, wexp,
+                               reinterpret_cast<hipStream_t>(stream));
+  SR_API_END
+}
+
+int sr_diag_colsum_fp8(const uint8_t* W8, const uint8_t* wexp, int N, int K, float* colsum, int device,
+                       void* stream) {
+  SR_API_BEGIN
+  SR_NONNULL(W8);
+  SR_NONNULL(wexp);
+  SR_NONNULL(colsum);
+  SR_CHECK(N > 0 && K > 0, "diag_colsum_fp8: N > 0, K > 0");
+  sr::DeviceGuard g(device);
+  sr::launch_colsum_fp8(W8, wexp, N, K, colsum, reinterpret_cast<hipStream_t>(stream));
+  SR_API_END
+}
+
+int sr_diag_fold_ln_weight(const float* w32, const float* gamma, const float* beta, const float* bias,
+                           int N, int K, void* w16, float* colsum, float* bias_out, int device,
+                           void* stream) {
+  SR_API_BEGIN
+  SR_NONNULL(w32);
+  SR_NONNULL(gamma);
+  SR_NONNULL(beta);
+  SR_NONNULL(bias);
+  SR_NONNULL(w16);
+  SR_NONNULL(colsum);
+  SR_NONNULL(bias_out);
+  SR_CHECK(N > 0 && K > 0, "diag_fold_ln_weight: N > 0, K > 0");
+  sr::DeviceGuard g(device);
+  sr::launch_fold_ln_weight(w32, gamma, beta, bias, N, K, reinterpret_cast<sr::half_t*>(w16), colsum,
+                            bias_out, reinterpret_cast<hipStream_t>(stream));
+  SR_API_END
+}
+
+int sr_diag_ln_stats_finalize(const float* stat, int nparts, float eps, int M, float* mr, int device,
+                              void* stream) {
+  SR_API_BEGIN
+  SR_NONNULL(stat);
+  SR_NONNULL(mr);
+  SR_CHECK(M > 0, "diag_ln_stats_finalize: M > 0");
+  SR_CHECK(nparts >= 1 && nparts <= 16, "diag_ln_stats_finalize: 1..16 partials per row");
+  SR_CHECK(eps > 0.f, "diag_ln_stats_finalize: eps > 0");
+  sr::DeviceGuard g(device);
+  sr::launch_ln_stats_finalize(stat, nparts, eps, M, mr, reinterpret_cast<hipStream_t>(stream));
+  SR_API_END
+}
+
 int sr_diag_mfma_rate(int f8, int blocks, int iters, float* sink, uint64_t* stamps, int device, void* stream) {
   SR_API_BEGIN
   SR_NONNULL(sink);

@@ -244,7 +244,7 @@ __global__ void convert_f32_f16_kernel(const float* __restrict__ in, half_t* __r
 }
 
 // LayerNorm folding of a projection weight (one workgroup per output row n):
-//   w16[n][k] = fp16(W[n][k] * gamma[k]);  colsum[n] = sum_k float(w16[n][k]);
+//   w16[n][k] = fp16(fp32(W[n][k] * gamma[k]));  colsum[n] = sum_k float(w16[n][k]);
 //   bias_out[n] = sum_k W[n][k] * beta[k] + bias[n]      (fp32 master weights)
 __global__ __launch_bounds__(256) void fold_ln_weight_kernel(const float* __restrict__ w32,
                                                              const float* __restrict__ gamma,
@@ -258,7 +258,11 @@ __global__ __launch_bounds__(256) void fold_ln_weight_kernel(const float* __rest
   float cs = 0.f, bs = 0.f;
   for (int k = tid; k < K; k += 256) {
     const float w = w32[(int64_t)n * K + k];
-    const half_t h = (half_t)(w * gamma[k]);
+    // (the fp32 product through an empty asm: fused with the conversion into v_fma_mixlo_f16
+    // (w, gamma, +0) it is rounded once, not twice as the oracle's, and -0 comes out as +0)
+    float wg = w * gamma[k];
+    asm("" : "+v"(wg));
+    const half_t h = (half_t)wg;
     w16[(int64_t)n * K + k] = h;
     cs += (float)h;
     bs = fmaf(w, beta[k], bs);

@@ -115,7 +115,7 @@ __device__ __forceinline__ uint32_t key_row(uint64_t key) { return 0xffffffffu -
 
 // OCP e4m3fn (bias 7, max 448, no infinities), round to nearest even, saturating at +-448.
 __device__ __forceinline__ uint32_t e4m3_rne(float v) {
-  const uint32_t sign = v < 0.f ? 0x80u : 0u;
+  const uint32_t sign = (__float_as_uint(v) >> 24) & 0x80u;  // the sign bit (v < 0 lost the sign of -0)
   const float a = fminf(fabsf(v), 448.f);
   if (a < 0.015625f) {  // below 2^-6: subnormal steps of 2^-9
     const uint32_t m = (uint32_t)rintf(a * 512.f);  // 0 .. 8 (8 = the smallest normal)

@@ -73,11 +73,6 @@ void launch_gemm_variant(int variant, int epi, const half_t* X, int64_t lda, con
                          const float* bias, const void* R, int64_t ldr, void* Y, int64_t ldy,
                          int M, int N, int K, hipStream_t stream, const LnFold* lf = nullptr);
 void gemm_force_tile(int t);  // test hook: -1 auto, else a GemmVariant
-// K1 for large query blocks (B in (128, 256]) on the pipelined GEMM: rows [r0, r1) of the corpus
-// against B queries; non-dense threshold mode only (same contract as launch_cosine_scan).
-// Y = epi(X8 . W8^T) on OCP e4m3 operands: X8 [M][K] bytes (lda bytes), W8 [N][K] bytes with
-// per-row E8M0 exponents lf->wexp[N] (W = W8 * 2^(wexp - 127)); K % 128 == 0, K >= 256;
-// epi in {EPI_LNF_F16, EPI_LNF_GELU_F8, EPI_RES16_STATS(_Y8), EPI_LNR16_STATS(_Y8)}.
 #if SR_WITH_DIAG
 // Diagnostic FFN1 launches (sr_diag_ffn1): diag 0 product, 2 no epilogue, 5 math only, 6 stores only.
 void launch_ffn1_diag(int diag, bool f8, const void* X, int64_t lda, const void* W, const uint8_t* wexp,
@@ -92,6 +87,10 @@ void launch_lnr_stats_stamps(const half_t* X, int64_t lda, const half_t* W, cons
                              int64_t ldr, const float* mr, const float* gamma, void* Y, int64_t ldy, int M,
                              int N, int K, float* stat_out, uint64_t* stamps, hipStream_t stream);
 #endif
+// Y = epi(X8 . W8^T) on OCP e4m3 operands: X8 [M][K] bytes (lda bytes), W8 [N][K] bytes with
+// per-row E8M0 exponents lf->wexp[N] (W = W8 * 2^(wexp - 127)); K % 128 == 0, K >= 256,
+// N % 256 == 0, lda % 16 == 0, ldy % 8 == 0, ldr % 8 == 0;
+// epi in {EPI_LNF_F16, EPI_LNF_GELU_F8, EPI_RES16_STATS(_Y8), EPI_LNR16_STATS(_Y8)}.
 void launch_gemm_f8w(int epi, const uint8_t* X8, int64_t lda, const uint8_t* W8, const float* bias,
                      const void* R, int64_t ldr, void* Y, int64_t ldy, int M, int N, int K,
                      hipStream_t stream, const LnFold* lf);
@@ -110,6 +109,8 @@ void launch_cosine_scan_gemm8(const uint8_t* corpus8, int64_t ld8, const uint8_t
 void launch_cosine_scan8(bool dense, const uint8_t* corpus8, int64_t ld8, const uint8_t* live,
                          int64_t r0, int64_t r1, const uint8_t* Q8, int B, const float* tau,
                          uint64_t* cand, int* cnt, int cap, hipStream_t s);
+// K1 for large query blocks (B in (128, 256]) on the pipelined GEMM: rows [r0, r1) of the corpus
+// against B queries; non-dense threshold mode only (same contract as launch_cosine_scan).
 void launch_cosine_scan_gemm(const half_t* corpus, int64_t ldc, const uint8_t* live, int64_t r0,
                              int64_t r1, const half_t* Q, int B, const float* tau, uint64_t* cand,
                              int* cnt, int cap, hipStream_t s);

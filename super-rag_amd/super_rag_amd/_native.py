@@ -256,6 +256,14 @@ DIAG_SIGNATURES = {
     "sr_diag_gemm_stats_y8": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
                                       c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int,
                                       c_int, c_void_p, c_int, c_void_p]),
+    "sr_diag_gemm_fold": (c_int, [c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64,
+                                  c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "sr_diag_quantize_rows_fp8": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "sr_diag_colsum_fp8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "sr_diag_fold_ln_weight": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                       c_void_p, c_void_p, c_int, c_void_p]),
+    "sr_diag_ln_stats_finalize": (c_int, [c_void_p, c_int, c_float, c_int, c_void_p, c_int, c_void_p]),
 }
 
 _lib = None
