@@ -451,7 +451,29 @@ int sr_lex_score_rows_weighted(sr_lex* x, const int64_t* qoff, const int32_t* qt
  * max||d^_j|| and the same bit-identity and -inf rules.  Quantisation changes what is stored, never how
  * it is scored.  Everything else (growth, remove, stats, both score entry points, the limits) is the
  * same on both dtypes.
- * Not provided: snapshots and compaction, a multi-device variant, a whole-corpus MaxSim scan,
+ *   sr_mv_dim       the index's dim (what a loaded index was saved with).
+ *   sr_mv_compact   drops the tombstoned rows, as sr_store_compact / sr_lex_compact do: kept rows keep
+ *                   their order, old_to_new (n_rows int64, may be NULL) receives the new row of a kept
+ *                   row and -1 for a dropped one, and equals the store's map for the same removals.
+ *                   Afterwards n_rows == n_live and n_tokens counts the kept rows' tokens.  In place:
+ *                   the pool is not duplicated and nothing is reallocated or shrunk; the kept bytes are
+ *                   moved, never re-quantised, so every score of a kept row keeps its bits.  The extra
+ *                   device memory is at most stage_bytes of staging (0: the default, 64 MiB) plus two
+ *                   int64 per kept row; stage_bytes below one token's bytes (dim * 2, dim for fp8) or
+ *                   negative is SR_ERR_INVALID and leaves the index untouched.  Blocking.
+ *   sr_mv_save      writes the whole state (tombstoned rows included) to `path` through "<path>.tmp",
+ *                   fsync and rename: a failed save leaves a previous snapshot intact.  Little endian:
+ *                   "SRMIMVX1", int32 dim, int32 dtype, int64 n_rows, int64 n_tokens, (n_rows + 1)
+ *                   int64 offsets, n_rows live bytes, n_tokens * dim * element size pool bytes as
+ *                   held in HBM.
+ *   sr_mv_load      the index a snapshot describes, on `device`; it scores bit for bit like the saved
+ *                   one and takes every call above.  The file is checked in full before any device
+ *                   work; SR_ERR_IO for: a wrong magic, dim not a multiple of 64 in [64, 1024], an
+ *                   unknown dtype, n_rows or n_tokens outside [0, 2^40], a size other than the header
+ *                   implies (truncated, or a trailing byte), off[0] != 0, decreasing offsets, a row of
+ *                   2^31 tokens or more, off[n_rows] != n_tokens, a live byte above 1, an e4m3 NaN code
+ *                   (0x7f, 0xff) in an fp8 pool.
+ * Not provided: a multi-device variant, shrinking the pool, a whole-corpus MaxSim scan,
  * per-token scales or residual codecs, quantised queries, a fused rerank entry point
  * (multivec.m3_rerank composes the existing ones).
  * ---------------------------------------------------------------------------------------------- */
@@ -471,6 +493,10 @@ int sr_mv_score_rows_dev(sr_mv* x, const void* q, const int32_t* q_len, int B, i
                          const int64_t* rows, int K, float* out_score, void* stream);
 int sr_mv_score_rows(sr_mv* x, const float* q, const int32_t* q_len, int B, int ld_q,
                      const int64_t* rows, int K, float* out_score);
+int sr_mv_dim(sr_mv* x, int* dim);
+int sr_mv_compact(sr_mv* x, int64_t stage_bytes, int64_t* old_to_new);
+int sr_mv_save(sr_mv* x, const char* path);
+int sr_mv_load(const char* path, int device, sr_mv** out);
 void sr_mv_destroy(sr_mv* x);
 
 /* Reciprocal-rank fusion of two ranked row lists per query (B x ka and B x kb, -1 padded), as

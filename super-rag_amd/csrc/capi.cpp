@@ -1338,6 +1338,41 @@ int sr_mv_score_rows(sr_mv* x, const float* q, const int32_t* q_len, int B, int 
   SR_API_END
 }
 
+int sr_mv_dim(sr_mv* x, int* dim) {
+  SR_API_BEGIN
+  SR_NONNULL(x);
+  SR_NONNULL(dim);
+  *dim = x->impl->dim();
+  SR_API_END
+}
+
+int sr_mv_compact(sr_mv* x, int64_t stage_bytes, int64_t* old_to_new) {
+  SR_API_BEGIN
+  SR_NONNULL(x);
+  std::lock_guard<std::mutex> lk(x->impl->mu);
+  x->impl->compact(stage_bytes, old_to_new);
+  SR_API_END
+}
+
+int sr_mv_save(sr_mv* x, const char* path) {
+  SR_API_BEGIN
+  SR_NONNULL(x);
+  SR_NONNULL(path);
+  std::lock_guard<std::mutex> lk(x->impl->mu);
+  x->impl->save(path);
+  SR_API_END
+}
+
+int sr_mv_load(const char* path, int device, sr_mv** out) {
+  SR_API_BEGIN
+  SR_NONNULL(out);
+  *out = nullptr;
+  SR_NONNULL(path);
+  sr::MultiVecIndex* mv = sr::MultiVecIndex::load(path, device);
+  *out = new sr_mv{mv};
+  SR_API_END
+}
+
 void sr_mv_destroy(sr_mv* x) {
   if (!x) return;
   delete x->impl;

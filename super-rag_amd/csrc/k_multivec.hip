@@ -40,6 +40,8 @@
 //     conversions per load.  The query stays the caller's fp16.
 //   - the factor 2^-8 is applied once, in fp32, to the finished sum (a power of two: exact).
 // Everything else, the fp16 instantiation included, is the code above unchanged.
+//
+// mv_move_kernel, at the end, is the byte mover of the index's in-place compaction (its own comment).
 #include <algorithm>
 #include <type_traits>
 
@@ -321,6 +323,45 @@ __global__ __launch_bounds__(256) void mv_pack_fp8_kernel(const half_t* __restri
   }
 }
 
+// Compaction move (multivec.hip MultiVecIndex::compact): the kept tokens [t0, t1) of the compacted
+// order, each copied from its old pool position to dst + (t - dst_t0) * row_bytes (dst: the pool
+// itself with dst_t0 = 0, or a staging buffer with dst_t0 = t0).  old_off / new_off [m] and new_off[m]:
+// the first token of every kept row before and after, new_off[0] <= t0 and t1 <= new_off[m].  A wave
+// owns whole tokens (grid-stride): one binary search in new_off per token, on wave-uniform values,
+// for the last kept row k with new_off[k] <= t (rows without tokens share their successor's offset
+// and are passed over), then row_bytes of 16-byte loads and stores, two per lane in flight.  Bytes
+// move as they are, whatever the dtype.  The caller guarantees that no source of the launch lies in
+// the range it writes.
+__global__ __launch_bounds__(256) void mv_move_kernel(const uint8_t* pool, uint8_t* dst, int64_t dst_t0,
+                                                      const int64_t* __restrict__ old_off,
+                                                      const int64_t* __restrict__ new_off, int64_t m,
+                                                      int64_t t0, int64_t t1, int row_bytes) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)((blockIdx.x * 256u + threadIdx.x) >> 6));
+  const int nwaves = (int)gridDim.x * 4;
+  const int units = row_bytes >> 4;
+  for (int64_t t = t0 + wave; t < t1; t += nwaves) {
+    int64_t lo = 0, hi = m;  // new_off[lo] <= t < new_off[hi]
+    while (hi - lo > 1) {
+      const int64_t mid = (lo + hi) >> 1;
+      if (new_off[mid] <= t)
+        lo = mid;
+      else
+        hi = mid;
+    }
+    const u32x4* s = reinterpret_cast<const u32x4*>(pool + (old_off[lo] + (t - new_off[lo])) * row_bytes);
+    u32x4* d = reinterpret_cast<u32x4*>(dst + (t - dst_t0) * row_bytes);
+    for (int u = lane; u < units; u += 128) {
+      const bool two = u + 64 < units;
+      const u32x4 a = s[u];
+      u32x4 b = a;
+      if (two) b = s[u + 64];
+      d[u] = a;
+      if (two) d[u + 64] = b;
+    }
+  }
+}
+
 }  // namespace
 
 void maxsim_check_args(int dim, int B, int ld_q, int K) {
@@ -389,6 +430,23 @@ void launch_mv_pack_fp8(const half_t* src, const int64_t* off, int64_t n, int64_
   ProfScope prof("mv_pack_fp8", s, 0.0, (double)n * ld_tok * dim * 3.0);
   hipLaunchKernelGGL(mv_pack_fp8_kernel, dim3((unsigned)n, (unsigned)by), dim3(256), 0, s, src, off, ld_tok,
                      dim, pool);
+  SR_LAUNCH_CHECK();
+}
+
+void launch_mv_move(const void* pool, void* dst, int64_t dst_t0, const int64_t* old_off,
+                    const int64_t* new_off, int64_t m, int64_t t0, int64_t t1, int row_bytes,
+                    hipStream_t s) {
+  if (t1 <= t0) return;
+  SR_CHECK(m >= 1 && row_bytes >= 64 && row_bytes % 64 == 0, "mv.compact: move arguments");
+  int dev = 0, cus = 0;
+  SR_HIP(hipGetDevice(&dev));
+  SR_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  // four tokens per workgroup and pass, eight workgroups per CU at the most
+  const int64_t grid = std::min<int64_t>(ceil_div(t1 - t0, 4), (int64_t)std::max(cus, 1) * 8);
+  ProfScope prof("mv_move", s, 0.0, (double)(t1 - t0) * row_bytes * 2.0);
+  hipLaunchKernelGGL(mv_move_kernel, dim3((unsigned)grid), dim3(256), 0, s,
+                     static_cast<const uint8_t*>(pool), static_cast<uint8_t*>(dst), dst_t0, old_off, new_off,
+                     m, t0, t1, row_bytes);
   SR_LAUNCH_CHECK();
 }
 

@@ -5,9 +5,14 @@
 // pool and the per-row arrays grow by doubling.  Every way into an fp8 pool goes through the one
 // quantising kernel (launch_mv_pack_fp8), so the stored bytes do not depend on it.  Appends and
 // removals finish before they return; scoring (k_multivec.hip) is asynchronous on the caller's
-// stream and ordered against them by the completion event, as in the store.
+// stream and ordered against them by the completion event, as in the store.  compact() drops the
+// tombstoned rows in place, with bounded staging; save() / load() write and read the whole state.
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <fstream>
+#include <string>
 #include <vector>
 
 #include "sr_kernels.h"
@@ -261,6 +266,256 @@ void MultiVecIndex::score_rows_host(const float* q, const int32_t* q_len, int B,
   score_rows_dev(dq, dlen, B, ld_q, drows, K, dout, stream_);
   SR_HIP(hipMemcpyAsync(out, dout, no * sizeof(float), hipMemcpyDeviceToHost, stream_));
   SR_HIP(hipStreamSynchronize(stream_));
+}
+
+// ---- compaction ----------------------------------------------------------------------------------
+// In place: the pool is never duplicated (an index sized to fill the card could not be compacted
+// otherwise).  Let t number the kept tokens in their order, which is also their position after the
+// compaction, and src(t) >= t be the pool position the token holds now; src(t) - t, the tokens dropped
+// before it, never decreases with t.  Tokens with src(t) == t stay where they are: everything before
+// the first dropped token.  The rest is cut into chunks [t0, t1) in ascending order; with gap =
+// src(t0) - t0, left = the tokens still to place and D = min(stage tokens, kDirectMinBytes of tokens):
+//   direct  (gap >= min(D, left))  t1 = t0 + min(gap, left): one launch of the move kernel, pool ->
+//           pool.  Every source of the chunk is >= src(t0) = t0 + gap >= t1, so the launch reads
+//           nothing it writes, whatever the order of its waves.
+//   staged  (otherwise)  t1 = t0 + min(stage tokens, left): the same kernel gathers the chunk into the
+//           staging buffer, then a device-to-device copy puts it at [t0, t1).  The gather writes no
+//           pool byte, and the copy starts after it in stream order.
+// A direct chunk moves its bytes once but is only as long as the gap, a staged one moves them twice
+// but is as long as the stage: below kDirectMinBytes per launch the launches of the direct path cost
+// more than the second pass of the staged one (an estimate, DESIGN.md: the stage was swept, this
+// threshold was not).
+// Between chunks the stream order is the only synchronisation, and it is enough: chunk c writes only
+// [t0, t1) of the pool, chunk c + 1 reads only src(t) >= t >= t1 for its own t >= t1, positions that
+// chunk c (and every earlier one, which wrote below t0) never wrote; they still hold the old bytes.
+// The staging buffer is rewritten by a gather only after the copy that read it, again by stream order.
+// Chunks are cut by tokens, so a row longer than the stage spans several; the kernel finds a token's
+// row in the kept rows' new offsets.
+namespace {
+struct MoveChunk {
+  int64_t t0, t1;
+  bool staged;
+};
+
+// old_off / new_off: the first token of every kept row before / after (new_off has one more entry, the
+// kept tokens), from the first kept row that moves (k0) on
+std::vector<MoveChunk> plan_moves(const std::vector<int64_t>& old_off, const std::vector<int64_t>& new_off,
+                                  int64_t stage_tok, int64_t direct_tok) {
+  std::vector<MoveChunk> plan;
+  if (old_off.empty()) return plan;
+  const int64_t T = new_off.back();
+  size_t k = 0;
+  for (int64_t t = new_off[0]; t < T; t = plan.back().t1) {
+    while (new_off[k + 1] <= t) ++k;  // the kept row of token t (t < T: k stays in range)
+    const int64_t gap = old_off[k] - new_off[k];
+    if (gap >= std::min(std::min(stage_tok, direct_tok), T - t))
+      plan.push_back({t, t + std::min(gap, T - t), false});
+    else
+      plan.push_back({t, t + std::min(stage_tok, T - t), true});
+  }
+  return plan;
+}
+}  // namespace
+
+void MultiVecIndex::compact(int64_t stage_bytes, int64_t* old_to_new) {
+  SR_CHECK(stage_bytes == 0 || stage_bytes >= (int64_t)row_bytes(),
+           "mv.compact: stage_bytes must be 0 (the default) or at least one token's bytes");
+  const int64_t stage_tok = (stage_bytes ? stage_bytes : kDefaultStageBytes) / (int64_t)row_bytes();
+  // the kept rows, the map and the offsets after the compaction
+  std::vector<int64_t> keep, noff{0};
+  keep.reserve((size_t)n_live_);
+  noff.reserve((size_t)n_live_ + 1);
+  for (int64_t r = 0; r < n_rows_; ++r) {
+    if (live_host_[(size_t)r]) {
+      if (old_to_new) old_to_new[r] = (int64_t)keep.size();
+      keep.push_back(r);
+      noff.push_back(noff.back() + (off_host_[(size_t)r + 1] - off_host_[(size_t)r]));
+    } else if (old_to_new) {
+      old_to_new[r] = -1;
+    }
+  }
+  const int64_t m = (int64_t)keep.size();
+  if (m == n_rows_) return;  // nothing is tombstoned: the identity
+  // from the first kept row whose tokens move
+  int64_t k0 = 0;
+  while (k0 < m && off_host_[(size_t)keep[(size_t)k0]] == noff[(size_t)k0]) ++k0;
+  std::vector<int64_t> mold, mnew;
+  for (int64_t k = k0; k < m; ++k) mold.push_back(off_host_[(size_t)keep[(size_t)k]]);
+  mnew.assign(noff.begin() + k0, noff.end());
+  const std::vector<MoveChunk> plan =
+      plan_moves(mold, mnew, stage_tok, std::max<int64_t>(1, kDirectMinBytes / (int64_t)row_bytes()));
+  int64_t stage_need = 0;
+  for (const MoveChunk& c : plan)
+    if (c.staged) stage_need = std::max(stage_need, c.t1 - c.t0);
+
+  DeviceGuard g(device_);
+  // every allocation before the first byte moves
+  DevBuf stage;
+  stage.reserve((size_t)stage_need * row_bytes());
+  int64_t *dold = nullptr, *dnew = nullptr;
+  if (!plan.empty()) {
+    Carve c;
+    c.part(mold.size(), &dold);
+    c.part(mnew.size(), &dnew);
+    hostio_.carve(c);
+  }
+  begin(stream_);
+  if (!plan.empty()) {
+    const int64_t mm = (int64_t)mold.size();
+    const int rb = (int)row_bytes();
+    SR_HIP(hipMemcpyAsync(dold, mold.data(), mold.size() * sizeof(int64_t), hipMemcpyHostToDevice, stream_));
+    SR_HIP(hipMemcpyAsync(dnew, mnew.data(), mnew.size() * sizeof(int64_t), hipMemcpyHostToDevice, stream_));
+    uint8_t* pool = pool_.as<uint8_t>();
+    for (const MoveChunk& ch : plan) {
+      if (ch.staged) {
+        launch_mv_move(pool, stage.p, ch.t0, dold, dnew, mm, ch.t0, ch.t1, rb, stream_);
+        SR_HIP(hipMemcpyAsync(pool + ch.t0 * rb, stage.p, (size_t)(ch.t1 - ch.t0) * rb,
+                              hipMemcpyDeviceToDevice, stream_));
+      } else {
+        launch_mv_move(pool, pool, 0, dold, dnew, mm, ch.t0, ch.t1, rb, stream_);
+      }
+    }
+  }
+  SR_HIP(hipMemcpyAsync(off_.p, noff.data(), noff.size() * sizeof(int64_t), hipMemcpyHostToDevice, stream_));
+  if (m > 0) SR_HIP(hipMemsetAsync(live_.p, 1, (size_t)m, stream_));
+  SR_HIP(hipMemsetAsync(live_.as<uint8_t>() + m, 0, (size_t)(n_rows_ - m), stream_));
+  end(stream_);
+  SR_HIP(hipStreamSynchronize(stream_));  // finished on return; the host vectors leave scope
+  off_host_ = noff;
+  live_host_.assign((size_t)m, 1);
+  n_rows_ = m;
+  n_live_ = m;
+  n_tokens_ = noff.back();
+}
+
+// ---- snapshots -----------------------------------------------------------------------------------
+// Snapshot format (little endian): "SRMIMVX1", int32 dim, int32 dtype (SR_DTYPE_F16 or
+// SR_DTYPE_FP8_E4M3), int64 n_rows, int64 n_tokens, (n_rows + 1) int64 offsets, n_rows bytes of live
+// flags, n_tokens x row_bytes pool bytes exactly as held in HBM (fp16 values, or e4m3 bytes; the
+// tokens of tombstoned rows included: the snapshot is the state).  Written to "<path>.tmp", fsync'd
+// and renamed over <path>, so a crash mid-save leaves the previous snapshot intact.
+static constexpr size_t kSnapshotChunkBytes = size_t(16) << 20;  // host buffer the pool streams through
+
+void MultiVecIndex::save(const char* path) {
+  DeviceGuard g(device_);
+  begin(stream_);
+  SR_HIP(hipStreamSynchronize(stream_));
+  const std::string tmp = std::string(path) + ".tmp";
+  std::ofstream f(tmp, std::ios::binary | std::ios::trunc);
+  if (!f) throw Error(SR_ERR_IO, std::string("mv.save: cannot open ") + tmp);
+  f.write("SRMIMVX1", 8);
+  const int32_t d = dim_, dt = dtype_;
+  f.write(reinterpret_cast<const char*>(&d), 4);
+  f.write(reinterpret_cast<const char*>(&dt), 4);
+  f.write(reinterpret_cast<const char*>(&n_rows_), 8);
+  f.write(reinterpret_cast<const char*>(&n_tokens_), 8);
+  f.write(reinterpret_cast<const char*>(off_host_.data()), (std::streamsize)((n_rows_ + 1) * sizeof(int64_t)));
+  f.write(reinterpret_cast<const char*>(live_host_.data()), (std::streamsize)n_rows_);
+  const int64_t step = std::max<int64_t>(1, (int64_t)(kSnapshotChunkBytes / row_bytes()));
+  std::vector<uint8_t> buf;
+  for (int64_t t = 0; t < n_tokens_ && f; t += step) {
+    const int64_t n = std::min(step, n_tokens_ - t);
+    buf.resize((size_t)n * row_bytes());
+    SR_HIP(hipMemcpyAsync(buf.data(), pool_.as<uint8_t>() + t * row_bytes(), buf.size(),
+                          hipMemcpyDeviceToHost, stream_));
+    SR_HIP(hipStreamSynchronize(stream_));
+    f.write(reinterpret_cast<const char*>(buf.data()), (std::streamsize)buf.size());
+  }
+  f.flush();
+  if (!f) {
+    f.close();
+    (void)std::remove(tmp.c_str());
+    throw Error(SR_ERR_IO, std::string("mv.save: write failed for ") + tmp);
+  }
+  f.close();
+  if (!fsync_path(tmp)) throw Error(SR_ERR_IO, std::string("mv.save: fsync failed for ") + tmp);
+  if (std::rename(tmp.c_str(), path) != 0)
+    throw Error(SR_ERR_IO, std::string("mv.save: cannot rename ") + tmp + " to " + path);
+}
+
+// Everything the file says is checked on the host before a device is touched, and no buffer is sized
+// by a header field before the file's real size has confirmed it.
+MultiVecIndex* MultiVecIndex::load(const char* path, int device) {
+  std::ifstream f(path, std::ios::binary);
+  if (!f) throw Error(SR_ERR_IO, std::string("mv.load: cannot open ") + path);
+  char magic[8];
+  f.read(magic, 8);
+  if (!f || std::memcmp(magic, "SRMIMVX1", 8) != 0)
+    throw Error(SR_ERR_IO, std::string("mv.load: not a multi-vector snapshot: ") + path);
+  int32_t d = 0, dt = 0;
+  int64_t n = 0, T = 0;
+  f.read(reinterpret_cast<char*>(&d), 4);
+  f.read(reinterpret_cast<char*>(&dt), 4);
+  f.read(reinterpret_cast<char*>(&n), 8);
+  f.read(reinterpret_cast<char*>(&T), 8);
+  const int64_t lim = int64_t(1) << 40;
+  if (!f || d < 64 || d > 1024 || d % 64 != 0 || (dt != SR_DTYPE_F16 && dt != SR_DTYPE_FP8_E4M3) ||
+      n < 0 || n > lim || T < 0 || T > lim)
+    throw Error(SR_ERR_IO, "mv.load: corrupt header");
+  const bool f8 = dt == SR_DTYPE_FP8_E4M3;
+  const int64_t rb = (int64_t)d * (f8 ? 1 : 2);
+  f.seekg(0, std::ios::end);
+  const std::streamoff size = f.tellg();
+  const int64_t pool_at = 32 + 8 * (n + 1) + n;
+  if (!f || size != (std::streamoff)(pool_at + T * rb))  // (< 2^52: the limits above)
+    throw Error(SR_ERR_IO, "mv.load: file size does not match the header (truncated or corrupt)");
+  f.seekg(32);
+  std::vector<int64_t> off((size_t)n + 1);
+  std::vector<uint8_t> live((size_t)n);
+  f.read(reinterpret_cast<char*>(off.data()), (std::streamsize)(off.size() * sizeof(int64_t)));
+  f.read(reinterpret_cast<char*>(live.data()), (std::streamsize)n);
+  if (!f) throw Error(SR_ERR_IO, "mv.load: truncated offsets or live flags");
+  if (off[0] != 0 || off[(size_t)n] != T) throw Error(SR_ERR_IO, "mv.load: offsets do not span the pool");
+  int64_t n_live = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    // (as unsigned: a difference of two corrupt offsets must not overflow)
+    const uint64_t len = (uint64_t)off[(size_t)i + 1] - (uint64_t)off[(size_t)i];
+    if (off[(size_t)i + 1] < off[(size_t)i] || len >= (uint64_t(1) << 31))
+      throw Error(SR_ERR_IO, "mv.load: offsets decrease or a row holds 2^31 tokens or more");
+    if (live[(size_t)i] > 1) throw Error(SR_ERR_IO, "mv.load: a live flag is neither 0 nor 1");
+    n_live += live[(size_t)i];
+  }
+  const int64_t step = std::max<int64_t>(1, (int64_t)kSnapshotChunkBytes / rb);
+  std::vector<uint8_t> buf;
+  if (f8) {  // the quantiser saturates and never writes a NaN code; get() and the kernel rely on it
+    for (int64_t t = 0; t < T; t += step) {
+      buf.resize((size_t)(std::min(step, T - t) * rb));
+      f.read(reinterpret_cast<char*>(buf.data()), (std::streamsize)buf.size());
+      if (!f) throw Error(SR_ERR_IO, "mv.load: truncated pool");
+      for (uint8_t c : buf)
+        if ((c & 0x7f) == 0x7f) throw Error(SR_ERR_IO, "mv.load: an fp8 pool holds a NaN code");
+    }
+    f.seekg((std::streamoff)pool_at);
+  }
+  MultiVecIndex* x = new MultiVecIndex(d, device, dt);
+  try {
+    DeviceGuard g(device);
+    x->ensure_capacity(n, T, x->stream_);
+    for (int64_t t = 0; t < T; t += step) {
+      buf.resize((size_t)(std::min(step, T - t) * rb));
+      f.read(reinterpret_cast<char*>(buf.data()), (std::streamsize)buf.size());
+      if (!f) throw Error(SR_ERR_IO, "mv.load: truncated pool");
+      SR_HIP(hipMemcpyAsync(x->pool_.as<uint8_t>() + t * rb, buf.data(), buf.size(), hipMemcpyHostToDevice,
+                            x->stream_));
+      SR_HIP(hipStreamSynchronize(x->stream_));  // `buf` is refilled
+    }
+    if (n > 0) {
+      SR_HIP(hipMemcpyAsync(x->off_.p, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice,
+                            x->stream_));
+      SR_HIP(hipMemcpyAsync(x->live_.p, live.data(), (size_t)n, hipMemcpyHostToDevice, x->stream_));
+    }
+    x->end(x->stream_);
+    SR_HIP(hipStreamSynchronize(x->stream_));
+    x->off_host_ = std::move(off);
+    x->live_host_ = std::move(live);
+    x->n_rows_ = n;
+    x->n_live_ = n_live;
+    x->n_tokens_ = T;
+  } catch (...) {
+    delete x;
+    throw;
+  }
+  return x;
 }
 
 }  // namespace sr

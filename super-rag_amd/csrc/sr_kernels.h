@@ -295,6 +295,13 @@ void launch_mv_pack(const half_t* src, const int64_t* off, int64_t n, int ld_tok
                     half_t* pool, hipStream_t s);
 void launch_mv_pack_fp8(const half_t* src, const int64_t* off, int64_t n, int64_t ld_tok, int dim,
                         uint8_t* pool, hipStream_t s);
+// compaction move: the kept tokens [t0, t1) of the compacted order from their old pool positions to
+// dst + (t - dst_t0) * row_bytes; old_off / new_off [m] (+ new_off[m]): the kept rows' first tokens
+// before and after (device), new_off[0] <= t0, t1 <= new_off[m].  Sources and [t0, t1) must not overlap
+// when dst is the pool.
+void launch_mv_move(const void* pool, void* dst, int64_t dst_t0, const int64_t* old_off,
+                    const int64_t* new_off, int64_t m, int64_t t0, int64_t t1, int row_bytes,
+                    hipStream_t s);
 
 // k_lex.hip — reciprocal-rank fusion of two ranked row lists per query (-1 padded), fp64 scores.
 void launch_rrf_fuse(const int64_t* rows_a, int ka, const int64_t* rows_b, int kb, int B,

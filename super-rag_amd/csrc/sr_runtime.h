@@ -510,6 +510,15 @@ class MultiVecIndex {
                       int K, float* out, hipStream_t s);
   void score_rows_host(const float* q, const int32_t* q_len, int B, int ld_q, const int64_t* rows,
                        int K, float* out);
+  // drops the tombstoned rows in place (kept rows keep their order; capacities stay): the kept
+  // tokens move down the pool in chunks, through at most stage_bytes of staging (0: the default);
+  // old_to_new (n_rows entries, may be null) as Store::compact writes it
+  void compact(int64_t stage_bytes, int64_t* old_to_new);
+  void save(const char* path);
+  static MultiVecIndex* load(const char* path, int device);
+  static constexpr int64_t kDefaultStageBytes = int64_t(64) << 20;
+  // a gap of this many bytes is enough for a chunk to move pool -> pool in one launch
+  static constexpr int64_t kDirectMinBytes = int64_t(16) << 20;
 
   std::mutex mu;
 

@@ -52,6 +52,38 @@ class NativeMultiVectorIndex:
         self.device = int(device)
         self._dtype = dtype
 
+    @classmethod
+    def load(cls, path: str, device: int = 0) -> "NativeMultiVectorIndex":
+        """The index a snapshot written by ``save`` describes (sr_mv_load); ``dim`` and the dtype
+        come from the file.  A file that breaks any rule of the format raises NativeError with
+        SR_ERR_IO before any device work."""
+        N.require_gpu()
+        h = ctypes.c_void_p()
+        N.call("sr_mv_load", path.encode(), int(device), ctypes.byref(h))
+        self = cls.__new__(cls)
+        self._h = h
+        dim, dt = ctypes.c_int(0), ctypes.c_int(0)
+        N.call("sr_mv_dim", h, ctypes.byref(dim))
+        N.call("sr_mv_info", h, ctypes.byref(dt), None)
+        self.dim = int(dim.value)
+        self.device = int(device)
+        self._dtype = {v: k for k, v in MV_DTYPES.items()}[int(dt.value)]
+        return self
+
+    def save(self, path: str) -> None:
+        """Write the whole state, tombstoned rows included (sr_mv_save): through ``path + ".tmp"``,
+        fsync and rename, so a failed save leaves a previous snapshot intact."""
+        N.call("sr_mv_save", self._h, path.encode())
+
+    def compact(self, stage_bytes: int = 0) -> np.ndarray:
+        """Drop the removed rows in place (sr_mv_compact) -> old_to_new [rows] int64, -1 for a
+        dropped row: the map NativeStore.compact returns for the same removals.  ``stage_bytes``
+        bounds the staging memory (0: the default 64 MiB; at least one token's bytes)."""
+        n = self.stats()["rows"]
+        m = np.empty(max(n, 1), dtype=np.int64)
+        N.call("sr_mv_compact", self._h, int(stage_bytes), N.ptr(m))
+        return m[:n]
+
     @property
     def dtype(self) -> str:
         """"fp16" or "fp8": how the tokens are stored."""
@@ -167,6 +199,35 @@ class NativeMultiVectorIndex:
             N.call("sr_mv_score_rows_dev", self._h, N.ptr(q), N.ptr(q_len), B, int(q.shape[1]), N.ptr(rows),
                    K, N.ptr(out), N.stream_handle(stream))
         return out
+
+
+def _rows_live(part):
+    """(rows, live) of a store (count()) or of a row-aligned index (stats())."""
+    if hasattr(part, "count"):
+        n, live = part.count()
+    else:
+        st = part.stats()
+        n, live = st["rows"], st["live"]
+    return int(n), int(live)
+
+
+def compact_aligned(store, mv, *others, stage_bytes: int = 0) -> np.ndarray:
+    """Compact a store, its token index and any further row-aligned indexes (impact / BM25) as one
+    step, so row i of each stays row i of the collection -> old_to_new [rows] int64 (the store's
+    map).  Raises ValueError, before anything is touched, unless every part reports the same
+    (rows, live); RuntimeError naming the part whose map differs from the store's (the parts had
+    different rows removed: the collection is then no longer aligned)."""
+    parts = [("store", store), ("multivec", mv)] + [(f"index {i + 1}", o) for i, o in enumerate(others)]
+    counts = [(name, _rows_live(p)) for name, p in parts]
+    if any(c != counts[0][1] for _, c in counts):
+        raise ValueError("compact_aligned: the parts are not row-aligned, (rows, live) = "
+                         + ", ".join(f"{name} {c}" for name, c in counts))
+    ref = np.asarray(store.compact(), dtype=np.int64)
+    for name, p in parts[1:]:
+        m = np.asarray(p.compact(stage_bytes) if p is mv else p.compact(), dtype=np.int64)
+        if m.shape != ref.shape or not np.array_equal(m, ref):
+            raise RuntimeError(f"compact_aligned: the map of {name} differs from the store's")
+    return ref
 
 
 def combine_dev(cos, maxsim, sparse, rows, k: int, weights=(1.0, 1.0, 1.0)):

@@ -20,6 +20,13 @@ three run the full last layer) on bge-m3's shape with seeded weights (vocabulary
 B = 64, S = 512 and B = 2, S = 8192, with the two added kernels' own times from the profiler.
 Every figure is the median of --repeats timed runs after a warm-up.  Prints one JSON line and writes it
 to --out.
+--compact runs part 3 alone and writes profiles/multivec_compact_bench.json: sr_mv_compact on an index of
+--pool-tokens tokens at dim 1024 (rows of 256 tokens), fp16 and fp8, with every second row or a random 10 %
+of the rows removed, at stage_bytes 16 / 64 / 256 MiB.  The call's wall time (it is blocking), median of
+--repeats after a warm-up, each on a freshly rebuilt index; the bytes of the tokens that move, read and
+written once, over that time, next to the copy yardstick counted the same way (a staged chunk moves its
+bytes twice, so its ceiling is half the yardstick); and the chunks and tokens the schedule sends down each
+path, from the planner's restatement in tests/mv_snapshot_ref.py.
 """
 import argparse
 import json
@@ -160,6 +167,68 @@ def bench_maxsim(a, copy_gbs):
     return out
 
 
+def bench_compact(a, copy_gbs):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import mv_snapshot_ref as R
+    dim, Ld = 1024, 256
+    n = a.pool_tokens // Ld
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(0)
+    step = min(n, (1 << 28) // (Ld * dim * 2))                # one 256 MiB block of tokens, added repeatedly
+    toks = unit_rows((step, Ld, dim), gen)
+    lens = torch.full((step,), Ld, dtype=torch.int32, device="cuda")
+    rng = np.random.default_rng(0)
+    patterns = {"every_second_row": np.arange(0, n, 2),
+                "random_10_percent": np.sort(rng.choice(n, n // 10, replace=False))}
+    out = []
+    for dtype in ("fp16", "fp8"):
+        rb = dim * ELEMENT_BYTES[dtype]
+        for pname, dead in patterns.items():
+            live = np.ones(n, bool)
+            live[dead] = False
+            src = R.sources([Ld] * n, live)
+            moved = int((src != np.arange(src.size)).sum())
+            for stage_mib in (16, 64, 256):
+                plan = R.plan([Ld] * n, live, (stage_mib << 20) // rb, R.DIRECT_MIN_BYTES // rb)
+                staged_tok = sum(t1 - t0 for t0, t1, s in plan if s)
+                ts, kernel = [], None
+                for it in range(a.repeats + 2):               # the first run is the warm-up, the last profiled
+                    profiled = it == a.repeats + 1
+                    x = NativeMultiVectorIndex(dim, dtype=dtype)
+                    for i in range(0, n, step):
+                        m = min(step, n - i)
+                        x.add_dev(toks[:m], lens[:m])
+                    x.remove(dead)
+                    torch.cuda.synchronize()
+                    if profiled:                              # the move kernel's own time, all launches of the call
+                        N.profile_enable(True)
+                        N.profile_read()
+                    t = time.perf_counter()
+                    x.compact(stage_mib << 20)
+                    ts.append((time.perf_counter() - t) * 1e3)
+                    if profiled:
+                        prof = N.profile_read()
+                        N.profile_enable(False)
+                        kernel = prof["mv_move"]["total_ms"] if "mv_move" in prof else None
+                    assert x.stats()["rows"] == int(live.sum())
+                    x.close()
+                ts = ts[1:-1]
+                ms = float(np.median(ts))
+                gbs = 2.0 * moved * rb / (ms * 1e-3) / 1e9
+                out.append({"dtype": dtype, "pattern": pname, "stage_MiB": stage_mib, "rows": n, "dead_rows": int(dead.size),
+                            "moved_bytes": moved * rb, "ms": round(ms, 3),
+                            "min_max_ms": [round(float(np.min(ts)), 3), round(float(np.max(ts)), 3)],
+                            "moved_GBs_read_plus_written": round(gbs, 1), "fraction_of_copy": round(gbs / copy_gbs, 3),
+                            # the kernel alone: every launch of one call, gathers into the stage included (the
+                            # stage -> pool copies are not kernels of the library and are not in it)
+                            "move_kernel_ms": None if kernel is None else round(kernel, 3),
+                            "move_kernel_GBs": None if not kernel else round(2.0 * moved * rb / (kernel * 1e-3) / 1e9, 1),
+                            "chunks_direct": sum(1 for c in plan if not c[2]), "chunks_staged": sum(1 for c in plan if c[2]),
+                            "staged_token_fraction": round(staged_tok / max(moved, 1), 3)})
+                print("# compact", out[-1], flush=True)
+    return out
+
+
 def bench_forward(a):
     from super_rag_amd.encoder import MODELS, Encoder, random_weights
     spec = replace(MODELS["bge-m3"], vocab_size=a.vocab)
@@ -200,9 +269,13 @@ def main():
     ap.add_argument("--skip-encoder", action="store_true")
     ap.add_argument("--dtype", choices=("fp16", "fp8", "both"), default="fp16",
                     help="token storage of the index; both: fp16 and fp8 over the same tokens, compared")
+    ap.add_argument("--compact", action="store_true",
+                    help="part 3 alone: sr_mv_compact, to profiles/multivec_compact_bench.json")
     ap.add_argument("--out", default=None,
                     help="default profiles/multivec_bench.json, profiles/multivec_fp8_bench.json with --dtype both")
     a = ap.parse_args()
+    if a.out is None and a.compact:
+        a.out = os.path.join(ROOT, "profiles", "multivec_compact_bench.json")
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", "multivec_fp8_bench.json" if a.dtype == "both" else "multivec_bench.json")
     os.environ.setdefault("SUPER_RAG_AMD_SYNTHETIC", "1")
@@ -211,9 +284,14 @@ def main():
     rec = {"metric": "sr_mv_score_rows_dev against the copy yardstick; multi-vector forward vs sparse / plain",
            "repeats": a.repeats, "statistic": "median of repeats after one warm-up call",
            "copy_yardstick_GBs": round(copy_gbs, 1), "pool_tokens": a.pool_tokens, "dtype": a.dtype}
-    rec["maxsim"] = bench_maxsim(a, copy_gbs)
-    if not a.skip_encoder:
-        rec["forward"] = bench_forward(a)
+    if a.compact:
+        rec["metric"] = "sr_mv_compact call time and moved bytes per second against the copy yardstick"
+        rec["statistic"] = "median of repeats after one warm-up, each on a freshly rebuilt index"
+        rec["compact"] = bench_compact(a, copy_gbs)
+    else:
+        rec["maxsim"] = bench_maxsim(a, copy_gbs)
+        if not a.skip_encoder:
+            rec["forward"] = bench_forward(a)
     line = json.dumps(rec)
     print(line, flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
