@@ -4,7 +4,8 @@
  * SR_WITH_DIAG=1), never by the product library libsrmi.so.  These entry points drive ONE kernel
  * on device buffers for single-kernel parity tests (tests/test_gpu_gemm.py, test_gpu_attention.py,
  * test_gpu_ffn1_epilogue.py, test_gpu_ffn1_gelu_sweep.py, test_gpu_gemm_f8_fold.py,
- * test_gpu_fold_helpers.py), microbenchmarks (tools/) and the measured peaks of bench.py; the
+ * test_gpu_fold_helpers.py, test_gpu_qkv_attention.py, test_gpu_attention_exact.py,
+ * test_gpu_cls_attn_fold.py), microbenchmarks (tools/) and the measured peaks of bench.py; the
  * timing-only variants return wrong results by design.  The diagnostic library also honours the
  * A/B environment knobs of DESIGN.md §4 (SR_GEMM_GROUP_M, SR_GEMM_STAGGER, SR_SCAN_CHUNK,
  * SR_SCAN_GROWTH, SR_SCAN_LEGACY, SR_SCAN_DIAG_NOEPI, SR_QA_DIAG, SR_FFN1_DIAG_WALKERS), which the
@@ -137,6 +138,31 @@ int sr_diag_gemm_lnr_stats_stamps(const void* X, int64_t lda, const void* W, con
 int sr_diag_qkv_attention_stamps(const void* X, int64_t lda, const void* W, const float* bias,
                                  const float* colsum, const float* mr, const int32_t* mask, void* ctx, int B,
                                  int S, int d, int heads, uint64_t* stamps, int device, void* stream);
+
+/* Diagnostic: K5c the way the encoder launches it (launch_qkv_attention without stamps, fp16 ctx):
+ * the product instantiations qkv_attn_kernel<false> (epi 0, EPI_BIAS_F16: Q | K | V = X W^T + bias;
+ * colsum / mr may be null) and qkv_attn_kernel<true> (epi 5, EPI_LNF_F16: rstd_m (X W^T - mu_m
+ * colsum) + bias, mr = (mu, rstd) per row).  X [B*S, lda] fp16 (lda >= d, lda % 8 == 0), W [3d, d]
+ * fp16, bias / colsum [3d] fp32, mask [B, S] int32, ctx [B*S, d] fp16; S == 128, d == 64 heads.
+ * The e4m3 ctx form (fp8 mode 5) is left out: that mode was rejected and exists only in the
+ * diagnostic library. */
+int sr_diag_qkv_attention(int epi, const void* X, int64_t lda, const void* W, const float* bias,
+                          const float* colsum, const float* mr, const int32_t* mask, void* ctx, int B, int S,
+                          int d, int heads, int device, void* stream);
+
+/* Diagnostic: the K/V-free CLS-only last layer's attention (launch_cls_attn_fold): w [B, H, D] fp16
+ * (the CLS query folded through W'_k per head), U [B*S, D] fp16 un-normalised rows, mr (mu, rstd)
+ * per row, mask [B, S] int32 -> z [B, 2 H D] fp16 = [hi(H D) | lo(H D)] of z'_h = sum_j p_j rstd_j
+ * (u_j - mu_j), p = softmax_j(rstd_j (w_h . u_j - mu_j sum(w_h)) / 8) over the live tokens.  D / H in
+ * {768 / 12, 1024 / 16}, S % 16 == 0, 16 <= S <= 512; every sequence needs a live token.  S <= 128
+ * runs the single-read form unless SR_CLS_FOLD_1READ=0 (read per launch). */
+int sr_diag_cls_attn_fold(const void* w, const void* U, const float* mr, const int32_t* mask, int B, int S,
+                          int D, int H, void* z, int device, void* stream);
+
+/* Diagnostic: the block-diagonal weights of that layer (launch_kv_blockdiag) from the folded QKV
+ * weight wqkv_f [3D, D] fp16: wk_bd [H D, D], wv_bd [D, 2 H D] fp16. */
+int sr_diag_kv_blockdiag(const void* wqkv_f, int D, int H, void* wk_bd, void* wv_bd, int device,
+                         void* stream);
 
 /* Diagnostic: the fp16 FFN1 of sr_diag_ffn1 with in-kernel s_memtime phase stamps (diag 9: the
  * product epilogue, 10: its math without the global stores, 11: the product epilogue without the

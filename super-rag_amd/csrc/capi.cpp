@@ -1772,6 +1772,59 @@ int sr_diag_qkv_attention_stamps(const void* X, int64_t lda, const void* W, cons
   SR_API_END
 }
 
+int sr_diag_qkv_attention(int epi, const void* X, int64_t lda, const void* W, const float* bias,
+                          const float* colsum, const float* mr, const int32_t* mask, void* ctx, int B, int S,
+                          int d, int heads, int device, void* stream) {
+  SR_API_BEGIN
+  SR_CHECK(epi == sr::EPI_BIAS_F16 || epi == sr::EPI_LNF_F16,
+           "diag_qkv_attention: epi must be BIAS_F16 (0) or LNF_F16 (5)");
+  SR_NONNULL(X);
+  SR_NONNULL(W);
+  SR_NONNULL(bias);
+  SR_NONNULL(mask);
+  SR_NONNULL(ctx);
+  SR_CHECK(epi != sr::EPI_LNF_F16 || (colsum && mr), "diag_qkv_attention: LNF needs colsum and mr");
+  sr::DeviceGuard g(device);
+  sr::LnFold lf;
+  const bool lnf = epi == sr::EPI_LNF_F16;
+  lf.mr = lnf ? mr : nullptr;
+  lf.colsum = lnf ? colsum : nullptr;
+  sr::launch_qkv_attention(epi, reinterpret_cast<const sr::half_t*>(X), lda,
+                           reinterpret_cast<const sr::half_t*>(W), bias, lnf ? &lf : nullptr, mask,
+                           reinterpret_cast<sr::half_t*>(ctx), B, S, d, heads,
+                           reinterpret_cast<hipStream_t>(stream), nullptr, nullptr);
+  SR_API_END
+}
+
+int sr_diag_cls_attn_fold(const void* w, const void* U, const float* mr, const int32_t* mask, int B, int S,
+                          int D, int H, void* z, int device, void* stream) {
+  SR_API_BEGIN
+  SR_NONNULL(w);
+  SR_NONNULL(U);
+  SR_NONNULL(mr);
+  SR_NONNULL(mask);
+  SR_NONNULL(z);
+  sr::DeviceGuard g(device);
+  sr::launch_cls_attn_fold(reinterpret_cast<const sr::half_t*>(w), reinterpret_cast<const sr::half_t*>(U), mr,
+                           mask, B, S, D, H, reinterpret_cast<sr::half_t*>(z),
+                           reinterpret_cast<hipStream_t>(stream));
+  SR_API_END
+}
+
+int sr_diag_kv_blockdiag(const void* wqkv_f, int D, int H, void* wk_bd, void* wv_bd, int device,
+                         void* stream) {
+  SR_API_BEGIN
+  SR_NONNULL(wqkv_f);
+  SR_NONNULL(wk_bd);
+  SR_NONNULL(wv_bd);
+  SR_CHECK(H >= 1 && D >= H && D % H == 0, "diag_kv_blockdiag: H >= 1 and D a multiple of H");
+  sr::DeviceGuard g(device);
+  sr::launch_kv_blockdiag(reinterpret_cast<const sr::half_t*>(wqkv_f), D, H,
+                          reinterpret_cast<sr::half_t*>(wk_bd), reinterpret_cast<sr::half_t*>(wv_bd),
+                          reinterpret_cast<hipStream_t>(stream));
+  SR_API_END
+}
+
 int sr_diag_attention(int variant, const void* qkv, const int32_t* mask, void* ctx, int B, int S,
                       int Sq, int d, int heads, int device, void* stream) {
   SR_API_BEGIN

@@ -177,7 +177,10 @@ void launch_vec_add(const float* a, const float* b, float* out, int n, hipStream
 void launch_quantize_norm_fp8(const half_t* u, int64_t ldu, const float* mr, int M, int d, uint8_t* x8,
                               hipStream_t s);
 // K/V-free CLS-only last layer (k_encoder_misc.hip): block-diagonal K / V weights from the folded
-// QKV weight, and per sequence scores + softmax + z' = sum_j p_j rstd_j (u_j - mu_j)
+// QKV weight, and per sequence scores + softmax + z' = sum_j p_j rstd_j (u_j - mu_j).
+// Contract: every sequence has at least one live token (the encoder's CLS token is always live);
+// an all-masked sequence divides by a zero softmax sum and is outside it.  U rows and mr entries
+// of masked tokens may hold any finite values (they meet a weight of exactly 0).
 bool cls_attn_fold_supported(int S, int D, int H);
 void launch_kv_blockdiag(const half_t* wqkv_f, int D, int H, half_t* wk_bd, half_t* wv_bd,
                          hipStream_t s);

@@ -250,6 +250,11 @@ DIAG_SIGNATURES = {
     "sr_diag_qkv_attention_stamps": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
                                              c_int, c_void_p]),
+    "sr_diag_qkv_attention": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "sr_diag_cls_attn_fold": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                      c_void_p, c_int, c_void_p]),
+    "sr_diag_kv_blockdiag": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
     "sr_diag_gemm_lnr_stats": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
                                        c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int,
                                        c_void_p, c_int, c_void_p]),
