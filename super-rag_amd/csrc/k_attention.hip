@@ -1285,7 +1285,10 @@ void launch_qkv_attention(int epi, const half_t* X, int64_t lda, const half_t* W
                           const LnFold* lf, const int32_t* mask, half_t* ctx, int B, int S, int d,
                           int heads, hipStream_t stream, uint8_t* ctx8, uint64_t* stamps) {
   SR_CHECK(qkv_attention_supported(S, d, heads), "qkv_attention: needs S == 128 and d_h == 64");
-  SR_CHECK(epi == EPI_BIAS_F16 || (epi == EPI_LNF_F16 && lf && lf->mr && lf->colsum && lf->stat_ld == 1),
+  static_assert(epi_traits(EPI_BIAS_F16).k5c && !epi_traits(EPI_BIAS_F16).lnf && epi_traits(EPI_LNF_F16).k5c &&
+                    epi_traits(EPI_LNF_F16).lnf, "the two qkv_attn_kernel forms below: plain and LN-folded");
+  const EpiTraits t = epi_traits(epi);  // (the k5c column: EPI_BIAS_F16, EPI_LNF_F16)
+  SR_CHECK(t.k5c && (!t.lnf || (lf && lf->mr && lf->colsum && lf->stat_ld == 1)),
            "qkv_attention: epilogue EPI_BIAS_F16 or EPI_LNF_F16 (row statistics + column sums)");
   SR_CHECK(lda >= d && lda % 8 == 0, "qkv_attention: lda must be >= d and a multiple of 8");
   if (B <= 0) return;
@@ -1295,18 +1298,13 @@ void launch_qkv_attention(int epi, const half_t* X, int64_t lda, const half_t* W
   const double bytes = 2.0 * M * d + (ctx8 ? 1.0 : 2.0) * M * d + 2.0 * 3 * d * (double)d + 4.0 * M;
   ProfScope prof("qkv_attention", stream, flops, bytes);
   const float scale_log2 = 1.4426950408889634f / 8.0f;
-  const int64_t tiles = ceil_div(M, 256) * heads;
+  const int64_t tiles = qkv_tiles(M, heads);
   SR_CHECK(tiles < (1ll << 31), "qkv_attention: too many tiles");
   // persistent: 8 XCD groups x G walkers, one 8-wave workgroup per CU (153 KiB of LDS)
-  const dim3 grid((unsigned)(8 * std::min<int64_t>(32, ceil_div(tiles, 8)))), block(512);
+  const dim3 grid(walker_grid(tiles)), block(512);
   // head groups of the tile walk (hg | heads): the walk takes every panel with heads [0, hg), then
-  // every panel with [hg, 2 hg), ...  An XCD's ~32 concurrent tiles then need ~32 / hg X panels
-  // (256 x d fp16) and hg W slices (192 x d fp16) in its 4 MiB L2: the divisor of heads that
-  // minimises 32 * 256 / hg + 192 hg (hg = 6 of 12 heads: 1,011 -> 1,033 TF/s and +0.9 % end to
-  // end against hg = heads; hg = 4 -5 %, profiles/r05_k5c_hgroup/)
-  int hg = heads;
-  for (int v = 1; v <= heads; ++v)
-    if (heads % v == 0 && 8192.0 / v + 192.0 * v <= 8192.0 / hg + 192.0 * hg) hg = v;
+  // every panel with [hg, 2 hg), ... (qkv_head_group, sr_gemm_plan.h)
+  int hg = qkv_head_group(heads);
 #if SR_WITH_DIAG
   if (const char* e = diag_getenv("SR_QA_HGROUP")) {
     const int v = std::atoi(e);

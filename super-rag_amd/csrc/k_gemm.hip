@@ -36,8 +36,6 @@ namespace sr {
 
 namespace {
 
-constexpr int GBK = 64;  // k per stage
-
 __device__ __forceinline__ int swz_chunk(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
 
 // Issue NI glds wave-instructions of one tile: instruction i of this wave fills LDS rows
@@ -422,10 +420,10 @@ __device__ __forceinline__ void store_tile_wide(float4v (&acc)[8][4], int nw0, i
                                                 const float2* __restrict__ gtab = nullptr,
                                                 const Pre& pre = Pre{}) {
   constexpr bool OUT8 = EPI == EPI_LNF_GELU_F8;  // e4m3 bytes instead of fp16
-  constexpr bool Y8 = EPI == EPI_RES16_STATS_Y8 || EPI == EPI_LNR16_STATS_Y8;  // + e4m3 copy
+  constexpr bool Y8 = epi_traits(EPI).y8;  // + e4m3 copy
   constexpr bool LNF = EPI == EPI_LNF_F16 || EPI == EPI_LNF_GELU_F16 || OUT8;
   constexpr bool RESN = EPI == EPI_BIAS_RES_F16 || EPI == EPI_RES16_STATS || EPI == EPI_RES16_STATS_Y8;
-  constexpr bool LNR = EPI == EPI_LNR16_STATS || EPI == EPI_LNR16_STATS_Y8;
+  constexpr bool LNR = epi_traits(EPI).lnr;
   constexpr bool STATS = (RESN && EPI != EPI_BIAS_RES_F16) || LNR;
   constexpr bool GELU = EPI == EPI_BIAS_GELU_F16;
   constexpr bool GELU2 = EPI == EPI_LNF_GELU_F16 || OUT8;  // stores 2 * GELU (consumer weight halved)
@@ -1069,8 +1067,8 @@ __device__ __forceinline__ void store_tile_res(float4v (&acc)[8][4], int nw0, in
                                                void* __restrict__ Y, int64_t ldy, const LnFold& lf,
                                                half_t* __restrict__ scr, const Pre& pre,
                                                const float* __restrict__ cst, int ln0, int lm0) {
-  constexpr bool Y8 = EPI == EPI_RES16_STATS_Y8 || EPI == EPI_LNR16_STATS_Y8;
-  constexpr bool LNR = EPI == EPI_LNR16_STATS || EPI == EPI_LNR16_STATS_Y8;
+  constexpr bool Y8 = epi_traits(EPI).y8;
+  constexpr bool LNR = epi_traits(EPI).lnr;
   static_assert(LNR || EPI == EPI_RES16_STATS || EPI == EPI_RES16_STATS_Y8, "store_tile_res: residual epilogues");
   static_assert(PERM, "store_tile_res: the W tile staged in perm32 order (8 consecutive columns per lane)");
   // (the lane recomputed here: the caller's copy, live across the K-loop, was spilled at 256 VGPRs
@@ -1449,7 +1447,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pipe_kernel(
   // RHALF: the persistent residual + statistics epilogues in half-tile order (store_tile_res): a
   // 2 KiB line scratch per wave and the same 4 KiB constants table ([256 bias][256 gamma][256 x
   // (mu, rstd)]; RES16: the bias only), the next tile's staging issued from inside the epilogue
-  constexpr bool RLNR = EPI == EPI_LNR16_STATS || EPI == EPI_LNR16_STATS_Y8;
+  constexpr bool RLNR = epi_traits(EPI).lnr;
   // (EPI_LNR16_STATS on fp16 operands only.  Round 5: the RES16 and fp8-operand instantiations
   // spilled 12-36 B in this form, profiles/r05_res_half/, r05_wexp_lds/.  Round 6: with the parked
   // statistics the RES16 and the e4m3-copy LNR (fp8 mode 3's O-projection) fit with no spills, and
@@ -1457,6 +1455,10 @@ __global__ __launch_bounds__(512, 2) void gemm_pipe_kernel(
   // 500.5 vs 500.5 q/s, one box (profiles/r06_res_half_y8/); left as they were.)
   constexpr bool RHALF = EPI == EPI_LNR16_STATS && !F8IN && LINE && PERSIST;
   constexpr bool CSTX = CSTL || RHALF;              // an epilogue constants table in LDS
+  // the launchers' persistence rules (sr_gemm_plan.h) are the host images of CSTL and RHALF
+  static_assert(DIAG != 0 || CSTL == (persist_min_ksteps(EPI) == 4), "CSTL epilogues need >= 4 K-steps when persistent");
+  static_assert(!(PERSIST && (DIAG == 0 || DIAG == 9)) || RHALF == persist_stages_row_stats(EPI, F8IN),
+                "RHALF stages consecutive row statistics: the host keeps it to stat_ld 1");
   constexpr int NCST = CSTL ? 4 : RHALF ? (RLNR ? 4 : 1) : 0;  // its 1 KiB pieces (one per wave)
   constexpr int LSCR = LINE ? (RHALF ? 8 * 1024 : 8 * 2048) : 0;
   constexpr int LDS_BASE = 2 * STAGE + LSCR + (GLINE ? 8 * 1024 : 0) + (CSTX ? 2048 : 0) + (SCAN ? 512 : 0) +
@@ -2121,8 +2123,7 @@ __global__ __launch_bounds__(256, 2) void gemm_pp_kernel(
 // chunks) that store their partial tiles to `part`, and gemm_chunk_reduce_kernel adds them in the
 // same order before the same epilogue: the outputs are bit-identical either way, so an embedding
 // never depends on the batch it was coalesced into.
-constexpr int KCHUNK = 6;
-constexpr int64_t kSplitMaxTiles = 128;  // split only below half a workgroup per CU slot pair
+// (KCHUNK, kSplitMaxTiles: sr_gemm_plan.h)
 
 template <int EPI, int BN, int BM, int WN, int WM, bool PERSIST>
 __global__ __launch_bounds__(64 * WN * WM, (WN * WM > 8) ? (WN * WM) / 4 : 2) void gemm_f16_kernel(
@@ -2292,16 +2293,20 @@ __global__ __launch_bounds__(256) void gemm_chunk_reduce_kernel(
   store_tile<EPI, 4, 4>(acc, n0 + (wave >> 1) * 64, m0 + (wave & 1) * 64, lane, M, bias, R, ldr, Y, ldy);
 }
 
-template <int BN, int BM, int WN, int WM, bool PERSIST>
-void launch_tile(int epi, dim3 grid, hipStream_t stream, const half_t* X, int64_t lda,
+// The family switches below keep one case list each (the lists and their order decide which kernels the
+// code object holds and in what order); each case asserts its family's column of epi_traits.
+
+// The 128 x 128 / 256 x 256 tile kernels (split-K: the chunk groups, then their reduction + epilogue)
+template <int BN, int BM, int WN, int WM>
+void launch_tile(const GemmPlan& p, int epi, hipStream_t stream, const half_t* X, int64_t lda,
                  const half_t* W, const float* bias, const void* R, int64_t ldr, void* Y,
-                 int64_t ldy, int M, int N, int K, int kxs, float4v* part = nullptr, int cpg = 0,
-                 int kchunk = 0) {
-  const dim3 block(64 * WN * WM);
+                 int64_t ldy, int M, int N, int K, float4v* part) {
+  const dim3 grid(p.grid_x, p.grid_y), block(p.block);
 #define SR_GEMM_CASE(E)                                                                        \
   case E:                                                                                      \
-    hipLaunchKernelGGL((gemm_f16_kernel<E, BN, BM, WN, WM, PERSIST>), grid, block, 0, stream, \
-                       X, lda, W, bias, R, ldr, Y, ldy, M, N, K, kxs, part, cpg, kchunk);      \
+    static_assert(epi_traits(E).tile, "tile family");                                          \
+    hipLaunchKernelGGL((gemm_f16_kernel<E, BN, BM, WN, WM, false>), grid, block, 0, stream,   \
+                       X, lda, W, bias, R, ldr, Y, ldy, M, N, K, p.kxs, part, p.cpg, p.kchunk); \
     if (part != nullptr)                                                                       \
       hipLaunchKernelGGL((gemm_chunk_reduce_kernel<E>), dim3(grid.x), dim3(256), 0, stream,    \
                          part, (int)ceil_div(K / GBK, KCHUNK), bias, R, ldr, Y, ldy, M, N);     \
@@ -2317,50 +2322,81 @@ void launch_tile(int epi, dim3 grid, hipStream_t stream, const half_t* X, int64_
 #undef SR_GEMM_CASE
 }
 
-}  // namespace
+// One case of the pipelined 256 x 256 kernels' switches (F8IN: fp8 operands, K and lda in 2-byte units)
+#define SR_PIPE_CASE(E, F8IN, TRAIT, x, la, w, k, lf)                                              \
+  case E:                                                                                        \
+    static_assert(epi_traits(E).TRAIT, "not in the " #TRAIT " column of epi_traits");            \
+    if (p.persist)                                                                               \
+      hipLaunchKernelGGL((gemm_pipe_kernel<E, true, 0, F8IN>), dim3(p.grid_x), dim3(p.block), 0,  \
+                         stream, x, la, w, bias, R, ldr, Y, ldy, M, N, k, lf);                   \
+    else                                                                                         \
+      hipLaunchKernelGGL((gemm_pipe_kernel<E, false, 0, F8IN>), dim3(p.grid_x), dim3(p.block), 0, \
+                         stream, x, la, w, bias, R, ldr, Y, ldy, M, N, k, lf);                   \
+    break;
 
-static const char* epi_name(int epi) {
-  switch (epi) {
-    case EPI_BIAS_F16: return "gemm_f16_bias";
-    case EPI_BIAS_GELU_F16: return "gemm_f16_bias_gelu";
-    case EPI_BIAS_RES_F32: return "gemm_f16_bias_residual";
-    case EPI_BIAS_RES_F16: return "gemm_f16_bias_residual16";
-    case EPI_LNF_F16: return "gemm_f16_lnfold";
-    case EPI_LNF_GELU_F16: return "gemm_f16_lnfold_gelu";
-    case EPI_RES16_STATS: return "gemm_f16_residual16_stats";
-    case EPI_LNR16_STATS: return "gemm_f16_lnres16_stats";
-    case EPI_LNF_GELU_F8: return "gemm_f16_lnfold_gelu_out8";
-    case EPI_RES16_STATS_Y8: return "gemm_f16_residual16_stats_y8";
-    case EPI_LNR16_STATS_Y8: return "gemm_f16_lnres16_stats_y8";
-    default: return "gemm_f16_bias_tanh";
-  }
+// K1 on the GEMM main loop, rows [r0, r0 + n) of the corpus: EPI_SCAN on fp16 rows of ld halfs, EPI_SCAN8
+// on e4m3 rows as 2-byte units (ld = row bytes / 2: the staging moves bytes)
+template <int EPI>
+void launch_scan(const half_t* rows0, int64_t ld, const uint8_t* live, int64_t r0, int64_t n,
+                 const half_t* Q, int B, const float* tau, uint64_t* cand, int* cnt, int cap, hipStream_t s) {
+  constexpr bool F8 = EPI == EPI_SCAN8;
+  const double rows = (double)n, elems = (double)(F8 ? 2 * ld : ld), row_bytes = 2.0 * ld;
+  ProfScope prof(F8 ? epi_traits(EPI).name_f8 : epi_traits(EPI).name_f16, s, 2.0 * rows * elems * B,
+                 rows * row_bytes + (double)B * row_bytes);
+  LnFold lf;
+  lf.stat_out = reinterpret_cast<float*>(cnt);  // (EPI_SCAN field re-use, see LnFold)
+  lf.stat_ld = r0;
+  auto kern = gemm_pipe_kernel<EPI, true>;
+#if SR_WITH_DIAG
+  static const bool diag_noepi = diag_getenv("SR_SCAN_DIAG_NOEPI") != nullptr;  // timing only
+  if (diag_noepi) kern = gemm_pipe_kernel<EPI, true, 2>;
+#endif
+  hipLaunchKernelGGL(kern, dim3(scan_grid(n)), dim3(512), 0, s, Q, ld, rows0, tau,
+                     (const void*)(live ? live + r0 : nullptr), (int64_t)0, (void*)cand, (int64_t)cap, B,
+                     (int)n, (int)ld, lf);
+  SR_LAUNCH_CHECK();
 }
 
-// Tile override for parity tests: SR_GEMM_TILE=small|big (read per launch), or gemm_force_tile().
+// SR_GEMM_STAGGER (diagnostic; read once): units of 512 cycles per phase (0 = off): > 0 de-phases the
+// walkers inside each XCD (their L2 working set spreads), < 0 the 8 XCDs against each other
+int stagger_env() {
+  static const int v = [] {
+    const char* e = diag_getenv("SR_GEMM_STAGGER");
+    return e ? std::atoi(e) : 0;
+  }();
+  return v;
+}
+
+// What the planner reads of a launch's arguments
+GemmAsk gemm_ask(bool f8, int variant, int epi, int64_t lda, int64_t ldr, int64_t ldy, int M, int N, int K,
+                 const LnFold* lf) {
+  GemmAsk a;
+  a.f8 = f8;
+  a.diag_build = SR_WITH_DIAG;
+  a.variant = variant;
+  a.epi = epi, a.M = M, a.N = N, a.K = K;
+  a.lda = lda, a.ldr = ldr, a.ldy = ldy;
+  if (lf) {
+    a.has_lf = true;
+    a.mr = lf->mr, a.colsum = lf->colsum, a.gamma = lf->gamma, a.stat_out = lf->stat_out;
+    a.y8 = lf->y8, a.wexp = lf->wexp;
+    a.stat_ld = lf->stat_ld, a.x_k = lf->x_k;
+    a.ws_bytes = lf->chunk_ws ? std::max<int64_t>(0, lf->chunk_ws_bytes) : -1;
+    a.group_m = lf->group_m, a.stagger = lf->stagger;
+  }
+  return a;
+}
+
+}  // namespace
+
 void launch_cosine_scan_gemm(const half_t* corpus, int64_t ldc, const uint8_t* live, int64_t r0,
                              int64_t r1, const half_t* Q, int B, const float* tau, uint64_t* cand,
                              int* cnt, int cap, hipStream_t s) {
   SR_CHECK(B > 0 && B <= 256, "cosine_scan_gemm: 1..256 queries");
   SR_CHECK(ldc % GBK == 0 && ldc >= 2 * GBK, "cosine_scan_gemm: padded dim must be a multiple of 64, >= 128");
   if (r1 <= r0) return;
-  const int64_t n = r1 - r0;
-  SR_CHECK(n < (1ll << 31), "cosine_scan_gemm: chunk too large");
-  const double rows = (double)n;
-  ProfScope prof("cosine_scan", s, 2.0 * rows * ldc * B, rows * ldc * 2.0 + (double)B * ldc * 2.0);
-  LnFold lf;
-  lf.stat_out = reinterpret_cast<float*>(cnt);  // (EPI_SCAN field re-use, see LnFold)
-  lf.stat_ld = r0;
-  const int64_t tiles = ceil_div(n, 256);
-  const dim3 grid((unsigned)(8 * std::min<int64_t>(32, ceil_div(tiles, 8)))), block(512);
-  auto kern = gemm_pipe_kernel<EPI_SCAN, true>;
-#if SR_WITH_DIAG
-  static const bool diag_noepi = diag_getenv("SR_SCAN_DIAG_NOEPI") != nullptr;  // timing only
-  if (diag_noepi) kern = gemm_pipe_kernel<EPI_SCAN, true, 2>;
-#endif
-  hipLaunchKernelGGL(kern, grid, block, 0, s, Q, ldc,
-                     corpus + r0 * ldc, tau, (const void*)(live ? live + r0 : nullptr), (int64_t)0,
-                     (void*)cand, (int64_t)cap, B, (int)n, (int)ldc, lf);
-  SR_LAUNCH_CHECK();
+  SR_CHECK(r1 - r0 < (1ll << 31), "cosine_scan_gemm: chunk too large");
+  launch_scan<EPI_SCAN>(corpus + r0 * ldc, ldc, live, r0, r1 - r0, Q, B, tau, cand, cnt, cap, s);
 }
 
 void launch_cosine_scan_gemm8(const uint8_t* corpus8, int64_t ld8, const uint8_t* live, int64_t r0,
@@ -2369,72 +2405,27 @@ void launch_cosine_scan_gemm8(const uint8_t* corpus8, int64_t ld8, const uint8_t
   SR_CHECK(B > 0 && B <= 256, "cosine_scan_gemm8: 1..256 queries");
   SR_CHECK(ld8 % 128 == 0 && ld8 >= 256, "cosine_scan_gemm8: row bytes must be a multiple of 128, >= 256");
   if (r1 <= r0) return;
-  const int64_t n = r1 - r0;
-  SR_CHECK(n < (1ll << 31), "cosine_scan_gemm8: chunk too large");
-  const double rows = (double)n;
-  ProfScope prof("cosine_scan8", s, 2.0 * rows * ld8 * B, rows * ld8 + (double)B * ld8);
-  LnFold lf;
-  lf.stat_out = reinterpret_cast<float*>(cnt);  // (EPI_SCAN field re-use, see LnFold)
-  lf.stat_ld = r0;
-  const int64_t tiles = ceil_div(n, 256);
-  const dim3 grid((unsigned)(8 * std::min<int64_t>(32, ceil_div(tiles, 8)))), block(512);
-  // operands as 2-byte units: K = ld8 / 2 (the staging moves bytes)
-  auto kern = gemm_pipe_kernel<EPI_SCAN8, true>;
-#if SR_WITH_DIAG
-  static const bool diag_noepi = diag_getenv("SR_SCAN_DIAG_NOEPI") != nullptr;  // timing only
-  if (diag_noepi) kern = gemm_pipe_kernel<EPI_SCAN8, true, 2>;
-#endif
-  hipLaunchKernelGGL(kern, grid, block, 0, s,
-                     reinterpret_cast<const half_t*>(Q8), ld8 / 2,
-                     reinterpret_cast<const half_t*>(corpus8 + r0 * ld8), tau,
-                     (const void*)(live ? live + r0 : nullptr), (int64_t)0, (void*)cand, (int64_t)cap,
-                     B, (int)n, (int)(ld8 / 2), lf);
-  SR_LAUNCH_CHECK();
+  SR_CHECK(r1 - r0 < (1ll << 31), "cosine_scan_gemm8: chunk too large");
+  launch_scan<EPI_SCAN8>(reinterpret_cast<const half_t*>(corpus8 + r0 * ld8), ld8 / 2, live, r0, r1 - r0,
+                         reinterpret_cast<const half_t*>(Q8), B, tau, cand, cnt, cap, s);
 }
 
 void launch_gemm_f8w(int epi, const uint8_t* X8, int64_t lda, const uint8_t* W8, const float* bias,
                      const void* R, int64_t ldr, void* Y, int64_t ldy, int M, int N, int K,
                      hipStream_t stream, const LnFold* lf) {
-  SR_CHECK(epi == EPI_LNF_F16 || epi == EPI_LNF_GELU_F8 || epi == EPI_RES16_STATS ||
-               epi == EPI_LNR16_STATS || epi == EPI_RES16_STATS_Y8 || epi == EPI_LNR16_STATS_Y8,
-           "gemm_f8w: unsupported epilogue");
-  const bool y8 = epi == EPI_RES16_STATS_Y8 || epi == EPI_LNR16_STATS_Y8;
-  const bool lnr = epi == EPI_LNR16_STATS || epi == EPI_LNR16_STATS_Y8;
-  const bool stats = lnr || epi == EPI_RES16_STATS || epi == EPI_RES16_STATS_Y8;
-  SR_CHECK(K % 128 == 0 && K >= 256, "gemm_f8w: K must be a multiple of 128, >= 256");
-  SR_CHECK(N % 256 == 0, "gemm_f8w: N must be a multiple of 256");
-  SR_CHECK(lda % 16 == 0 && ldy % 8 == 0 && ldr % 8 == 0, "gemm_f8w: 16-byte rows");
-  SR_CHECK(lf && lf->wexp, "gemm_f8w: the weight rows' exponents (LnFold.wexp)");
-  SR_CHECK((stats && !lnr) || lf->mr, "gemm_f8w: LN-folded operand needs its row statistics");
-  SR_CHECK(stats || lf->colsum, "gemm_f8w: LNF needs colsum");
-  SR_CHECK(epi != EPI_LNF_GELU_F8 || lf->stat_ld == 1, "gemm_f8w: FFN1 reads consecutive row statistics");
-  SR_CHECK(!lnr || lf->gamma, "gemm_f8w: LNR needs the LayerNorm weight");
-  SR_CHECK(!stats || lf->stat_out, "gemm_f8w: stat_out");
-  SR_CHECK(!y8 || lf->y8, "gemm_f8w: the e4m3-copy epilogues need LnFold.y8");
+  const GemmAsk a = gemm_ask(true, -1, epi, lda, ldr, ldy, M, N, K, lf);
+  const char* bad = check_gemm_args(a);
+  SR_CHECK(!bad, bad);
   if (M <= 0) return;
-  const char* name = epi == EPI_LNF_F16 ? "gemm_f8_lnfold" : epi == EPI_LNF_GELU_F8 ? "gemm_f8_lnfold_gelu_out8"
-                     : !stats ? "gemm_f8" : !lnr ? (y8 ? "gemm_f8_residual16_stats_y8" : "gemm_f8_residual16_stats")
-                     : (y8 ? "gemm_f8_lnres16_stats_y8" : "gemm_f8_lnres16_stats");
-  const double out_b = epi == EPI_LNF_GELU_F8 ? 1.0 : 2.0, res_b = stats ? 2.0 : 0.0;
-  ProfScope prof(name, stream, 2.0 * M * (double)N * K,
-                 (double)M * K + (double)N * K + (out_b + res_b + (y8 ? 1.0 : 0.0)) * (double)M * N);
-  const LnFold lfv = *lf;
-  const int64_t tiles = (int64_t)(N / 256) * ceil_div(M, 256);
-  // (the FFN1 epilogue's constants are staged during K-step 1 of a persistent tile: nk >= 4)
-  const bool persist = tiles >= 512 && (epi != EPI_LNF_GELU_F8 || K / 2 >= 4 * 64);
-  const dim3 grid(persist ? (unsigned)(8 * std::min<int64_t>(32, ceil_div(tiles, 8))) : (unsigned)tiles);
+  const GemmPlan p = plan_gemm(a);
+  ProfScope prof(p.name, stream, p.flops, p.bytes);
   // operands as 2-byte units: K / 2, lda / 2 (the staging moves bytes)
   const half_t* x = reinterpret_cast<const half_t*>(X8);
   const half_t* w = reinterpret_cast<const half_t*>(W8);
-#define SR_F8_CASE(E)                                                                            \
-  case E:                                                                                        \
-    if (persist)                                                                                 \
-      hipLaunchKernelGGL((gemm_pipe_kernel<E, true, 0, true>), grid, dim3(512), 0, stream, x,     \
-                         lda / 2, w, bias, R, ldr, Y, ldy, M, N, K / 2, lfv);                    \
-    else                                                                                         \
-      hipLaunchKernelGGL((gemm_pipe_kernel<E, false, 0, true>), grid, dim3(512), 0, stream, x,    \
-                         lda / 2, w, bias, R, ldr, Y, ldy, M, N, K / 2, lfv);                    \
-    break;
+  LnFold lfv = *lf;
+  lfv.group_m = p.group_m;  // (the plan passes both through as the caller set them: no product walk,
+  lfv.stagger = p.stagger;  //  no de-phasing on fp8 operands today)
+#define SR_F8_CASE(E) SR_PIPE_CASE(E, true, f8, x, lda / 2, w, K / 2, lfv)
   switch (epi) {
     SR_F8_CASE(EPI_LNF_F16)
     SR_F8_CASE(EPI_LNF_GELU_F8)
@@ -2473,8 +2464,8 @@ void launch_ffn1_diag(int diag, bool f8, const void* X, int64_t lda, const void*
     return;
   }
   SR_CHECK(!f8 || (wexp && K % 128 == 0), "ffn1_diag: fp8 needs wexp, K % 128 == 0");
-  SR_CHECK((f8 ? K / 2 : K) >= 4 * 64, "ffn1_diag: the persistent FFN1 needs >= 4 K-steps");
-  const int64_t tiles = (int64_t)(N / 256) * ceil_div(M, 256);
+  const int kk = f8 ? K / 2 : K;  // (fp8 operands as 2-byte units)
+  SR_CHECK(kk / GBK >= persist_min_ksteps(EPI_LNF_GELU_F16), "ffn1_diag: the persistent FFN1 needs >= 4 K-steps");
   // SR_FFN1_DIAG_WALKERS = walkers per XCD (1..32; default 32 = every CU): with fewer CUs storing
   // at once, a store cost that is the chip's write bandwidth shrinks, a per-CU one does not
   static const int walkers = [] {
@@ -2482,18 +2473,14 @@ void launch_ffn1_diag(int diag, bool f8, const void* X, int64_t lda, const void*
     const int w = e ? std::atoi(e) : 32;
     return w < 1 ? 1 : (w > 32 ? 32 : w);
   }();
-  const dim3 grid((unsigned)(8 * std::min<int64_t>(walkers, ceil_div(tiles, 8)))), block(512);
-  lf.group_m = K <= 1024 ? (N >= 2048 ? 8 : 4) : 0;  // the product walk
-  {  // the product's walker de-phasing (SR_GEMM_STAGGER, launch_gemm)
-    const char* e = diag_getenv("SR_GEMM_STAGGER");
-    const int st = e ? std::atoi(e) : 0;
-    lf.stagger = st > 0 ? std::max(1, st * K / 768) : st < 0 ? std::min(-1, st * K / 768) : 0;
-  }
+  const dim3 grid(walker_grid((int64_t)(N / 256) * ceil_div(M, 256), walkers)), block(512);
+  lf.group_m = product_group_m(N, K);  // the product's walk and walker de-phasing (on K as passed)
+  const char* st = diag_getenv("SR_GEMM_STAGGER");  // (read per call here: in-process sweeps through sr_diag_ffn1)
+  lf.stagger = stagger_phase(st ? std::atoi(st) : 0, K);
   ProfScope prof(f8 ? "ffn1_diag_f8" : "ffn1_diag", stream, 2.0 * M * (double)N * K, 0.0);
   const half_t* x = reinterpret_cast<const half_t*>(X);
   const half_t* w = reinterpret_cast<const half_t*>(W);
   const int64_t la = f8 ? lda / 2 : lda;
-  const int kk = f8 ? K / 2 : K;
 #define SR_FD(D)                                                                                  \
   if (f8)                                                                                         \
     hipLaunchKernelGGL((gemm_pipe_kernel<EPI_LNF_GELU_F8, true, D, true>), grid, block, 0, stream, \
@@ -2535,9 +2522,8 @@ void launch_lnr_stats_stamps(const half_t* X, int64_t lda, const half_t* W, cons
   lf.gamma = gamma;
   lf.stat_out = stat_out;
   lf.y8 = reinterpret_cast<uint8_t*>(stamps);  // (the non-Y8 epilogue has no e4m3 copy)
-  lf.group_m = K <= 1024 ? (N >= 2048 ? 8 : 4) : 0;  // the product walk
-  const int64_t tiles = (int64_t)(N / 256) * ceil_div(M, 256);
-  const dim3 grid((unsigned)(8 * std::min<int64_t>(32, ceil_div(tiles, 8)))), block(512);
+  lf.group_m = product_group_m(N, K);
+  const dim3 grid(walker_grid((int64_t)(N / 256) * ceil_div(M, 256))), block(512);
   hipLaunchKernelGGL((gemm_pipe_kernel<EPI_LNR16_STATS, true, 9>), grid, block, 0, stream, X, lda, W, bias, R, ldr,
                      Y, ldy, M, N, K, lf);
   SR_LAUNCH_CHECK();
@@ -2597,6 +2583,8 @@ void launch_quantize_rows_fp8(const half_t* W, int N, int K, uint8_t* W8, uint8_
   SR_LAUNCH_CHECK();
 }
 
+// Tile override for parity tests: SR_GEMM_TILE=small|big|pipe|pipe_persist|pp (read per launch), or
+// gemm_force_tile().
 static int g_force_tile = -1;
 void gemm_force_tile(int t) { g_force_tile = t; }
 static int forced_tile() {
@@ -2611,69 +2599,10 @@ static int forced_tile() {
   return -1;
 }
 
-void launch_gemm(int epi, const half_t* X, int64_t lda, const half_t* W, const float* bias,
-                 const void* R, int64_t ldr, void* Y, int64_t ldy, int M, int N, int K,
-                 hipStream_t stream, const LnFold* lf) {
-  launch_gemm_variant(-1, epi, X, lda, W, bias, R, ldr, Y, ldy, M, N, K, stream, lf);
-}
-
-void launch_gemm_variant(int variant, int epi, const half_t* X, int64_t lda, const half_t* W,
-                         const float* bias, const void* R, int64_t ldr, void* Y, int64_t ldy,
-                         int M, int N, int K, hipStream_t stream, const LnFold* lf) {
-  SR_CHECK(K % GBK == 0, "gemm: K must be a multiple of 64");
-  SR_CHECK(N % 128 == 0, "gemm: N must be a multiple of 128");
-  SR_CHECK(lda % 8 == 0 && ldy % 4 == 0, "gemm: leading dimensions must keep 16-byte rows");
-  const bool fold = epi >= EPI_LNF_F16;
-  SR_CHECK((epi >= 0 && epi <= EPI_LNR16_STATS) || epi == EPI_LNF_GELU_F8 ||
-               epi == EPI_RES16_STATS_Y8 || epi == EPI_LNR16_STATS_Y8, "gemm: unknown epilogue");
-  SR_CHECK(!(epi == EPI_RES16_STATS_Y8 || epi == EPI_LNR16_STATS_Y8) || (lf && lf->y8),
-           "gemm: the e4m3-copy epilogues need LnFold.y8");
-  SR_CHECK(!fold || (lf && N % 256 == 0), "gemm: LayerNorm-folded epilogues need LnFold, N % 256");
-  SR_CHECK(!(epi == EPI_LNF_F16 || epi == EPI_LNF_GELU_F16 || epi == EPI_LNF_GELU_F8 ||
-             epi == EPI_LNR16_STATS || epi == EPI_LNR16_STATS_Y8) || lf->mr,
-           "gemm: LN-folded operand needs its row statistics");
-  SR_CHECK(!(epi == EPI_LNF_F16 || epi == EPI_LNF_GELU_F16 || epi == EPI_LNF_GELU_F8) || lf->colsum,
-           "gemm: LNF needs colsum");
-  SR_CHECK(!(epi == EPI_LNF_GELU_F16 || epi == EPI_LNF_GELU_F8) || lf->stat_ld == 1,
-           "gemm: the FFN1 epilogues read consecutive row statistics (stat_ld 1)");
-  SR_CHECK(!(epi == EPI_LNR16_STATS || epi == EPI_LNR16_STATS_Y8) || lf->gamma,
-           "gemm: LNR needs the LayerNorm weight");
-  SR_CHECK(!(epi == EPI_RES16_STATS || epi == EPI_LNR16_STATS || epi == EPI_RES16_STATS_Y8 ||
-             epi == EPI_LNR16_STATS_Y8) || lf->stat_out,
-           "gemm: *_STATS epilogue needs stat_out");
-  const int x_k = lf && lf->x_k > 0 ? lf->x_k : K;
-  SR_CHECK(x_k == K || (K == 2 * x_k && x_k % GBK == 0 && epi < EPI_LNF_GELU_F8),
-           "gemm: split weights need K == 2 x_k (x_k % 64 == 0, fp16 operands)");
-  if (M <= 0) return;
-  const bool out32 = epi == EPI_BIAS_RES_F32 || epi == EPI_BIAS_TANH_F32;
-  const double out_b = out32 ? 4.0 : epi == EPI_LNF_GELU_F8 ? 1.0 : 2.0;
-  const double res_b = epi == EPI_BIAS_RES_F32 ? 4.0
-                       : (epi == EPI_BIAS_RES_F16 || epi == EPI_RES16_STATS || epi == EPI_LNR16_STATS ||
-                          epi == EPI_RES16_STATS_Y8 || epi == EPI_LNR16_STATS_Y8) ? 2.0
-                                                                                                     : 0.0;
-  const double bytes = 2.0 * ((double)M * x_k + (double)N * K) + (out_b + res_b) * (double)M * N;
-  ProfScope prof(epi_name(epi), stream, 2.0 * M * (double)N * K, bytes);
-  const int64_t big_tiles = (N % 256 == 0) ? (int64_t)(N / 256) * ceil_div(M, 256) : 0;
-  SR_CHECK(big_tiles < (1ll << 31), "gemm: too many tiles");
-  int v = variant >= 0 ? variant : forced_tile();
-  if (v < 0) v = big_tiles >= 512 ? GEMM_PIPE_PERSIST : GEMM_SMALL;
-  if (v != GEMM_SMALL && N % 256 != 0) v = GEMM_SMALL;
-  if (v == GEMM_PP && (K % 32 != 0 || epi >= EPI_LNF_GELU_F8 || x_k != K)) v = GEMM_PIPE;
-  if (x_k != K && v >= GEMM_DIAG_NOLOAD && v != GEMM_PP) v = GEMM_PIPE;  // diagnostics: plain K
-  SR_CHECK(SR_WITH_DIAG || !(v == GEMM_DIAG_NOLOAD || v == GEMM_DIAG_NOEPI ||
-                             (v >= GEMM_DIAG_P_NOEPI && v <= GEMM_DIAG_P_STOREONLY)),
-           "gemm: timing-only variants are in the diagnostic library (libsrmi_diag.so)");
-  if (fold && (v == GEMM_SMALL || v == GEMM_BIG)) v = big_tiles >= 512 ? GEMM_PIPE_PERSIST : GEMM_PIPE;
-  const bool wide = (v == GEMM_PIPE || v == GEMM_PIPE_PERSIST || v == GEMM_PP) && !out32;
-  SR_CHECK(!wide || (ldy % 8 == 0 && ldr % 8 == 0), "gemm: fp16 outputs need ldy, ldr % 8 == 0");
-  SR_CHECK(epi < EPI_LNF_GELU_F8 || v == GEMM_PIPE || v == GEMM_PIPE_PERSIST,
-           "gemm: the e4m3-output epilogues run on the pipelined kernels");
-  LnFold lfv = lf ? *lf : LnFold{};
-  // Short-K GEMMs (K <= 1024: QKV, FFN1, O-proj) walk groups of 8 (N >= 2048) or 4 m-panels;
-  // FFN2 (K = 3072) stays n fastest.  Same-box A/B of the full bench: 422.8 / 424.0 -> 429.8 /
-  // 431.0 q/s (profiles/r01_gemm_group_m.log).  SR_GEMM_GROUP_M overrides (diagnostic).
-  // (diagnostic) SR_GEMM_GROUP_M = "G" for every shape, or "N:G,N:G,..." per output width N
-  static const std::vector<std::pair<int, int>> group_m_env = [] {
+// (diagnostic; read once) SR_GEMM_GROUP_M = "G" for every shape (N = -1), or "N:G,N:G,..." per output
+// width N: overrides product_group_m
+static const std::vector<std::pair<int, int>>& group_m_env() {
+  static const std::vector<std::pair<int, int>> env = [] {
     std::vector<std::pair<int, int>> v;
     const char* e = diag_getenv("SR_GEMM_GROUP_M");
     if (!e) return v;
@@ -2692,119 +2621,94 @@ void launch_gemm_variant(int variant, int epi, const half_t* X, int64_t lda, con
     }
     return v;
   }();
-  lfv.group_m = K <= 1024 ? (N >= 2048 ? 8 : 4) : 0;
-  for (const auto& [n_env, g_env] : group_m_env)
-    if (n_env < 0 || n_env == N) lfv.group_m = g_env;
-  lfv.x_k = x_k == K ? 0 : x_k;
-  // de-phasing of the persistent walkers: phase step ~1/16 of a tile (K / 96 x 512 cycles);
-  // SR_GEMM_STAGGER = units of 512 cycles per phase (0 = off): > 0 de-phases the walkers inside
-  // each XCD (their L2 working set spreads), < 0 the 8 XCDs against each other (diagnostic)
-  static const int stagger_env = [] {
-    const char* e = diag_getenv("SR_GEMM_STAGGER");
-    return e ? std::atoi(e) : 0;
-  }();
-  lfv.stagger = stagger_env > 0 ? std::max(1, stagger_env * K / 768)
-                : stagger_env < 0 ? std::min(-1, stagger_env * K / 768) : 0;
-  if (v == GEMM_BIG) {
-    launch_tile<256, 256, 2, 4, false>(epi, dim3((unsigned)big_tiles), stream, X, lda, W, bias, R,
-                                       ldr, Y, ldy, M, N, K, x_k / GBK);
+  return env;
+}
+
+void launch_gemm(int epi, const half_t* X, int64_t lda, const half_t* W, const float* bias,
+                 const void* R, int64_t ldr, void* Y, int64_t ldy, int M, int N, int K,
+                 hipStream_t stream, const LnFold* lf) {
+  launch_gemm_variant(-1, epi, X, lda, W, bias, R, ldr, Y, ldy, M, N, K, stream, lf);
+}
+
+void launch_gemm_variant(int variant, int epi, const half_t* X, int64_t lda, const half_t* W,
+                         const float* bias, const void* R, int64_t ldr, void* Y, int64_t ldy,
+                         int M, int N, int K, hipStream_t stream, const LnFold* lf) {
+  GemmAsk a = gemm_ask(false, variant, epi, lda, ldr, ldy, M, N, K, lf);
+  const char* bad = check_gemm_args(a);
+  SR_CHECK(!bad, bad);
+  if (M <= 0) return;
+  a.forced_tile = variant >= 0 ? -1 : forced_tile();
+  for (const auto& [n_env, g_env] : group_m_env())
+    if (n_env < 0 || n_env == N) a.group_m_override = true, a.group_m_env = g_env;
+  a.stagger_env = stagger_env();
+  const GemmPlan p = plan_gemm(a);
+  ProfScope prof(p.name, stream, p.flops, p.bytes);  // (a call the plan rejects is booked too, as before)
+  SR_CHECK(!p.error, p.error);
+  LnFold lfv = lf ? *lf : LnFold{};
+  lfv.group_m = p.group_m;
+  lfv.x_k = p.x_k;
+  lfv.stagger = p.stagger;
+  switch (p.family) {
+    case FAM_TILE256:
+      launch_tile<256, 256, 2, 4>(p, epi, stream, X, lda, W, bias, R, ldr, Y, ldy, M, N, K, nullptr);
+      break;
 #if SR_WITH_DIAG
-  } else if (v >= GEMM_DIAG_P_NOEPI && v <= GEMM_DIAG_P_STOREONLY) {
-    const int64_t g = 8 * std::min<int64_t>(32, ceil_div(big_tiles, 8));
-    const dim3 grid((unsigned)g), block(512);
-    if (v == GEMM_DIAG_P_NOEPI)
-      hipLaunchKernelGGL((gemm_pipe_kernel<EPI_BIAS_F16, true, 2>), grid, block, 0, stream, X, lda,
-                         W, bias, R, ldr, Y, ldy, M, N, K, lfv);
-    else if (v == GEMM_DIAG_P_MATHONLY)
-      hipLaunchKernelGGL((gemm_pipe_kernel<EPI_BIAS_F16, true, 3>), grid, block, 0, stream, X, lda,
-                         W, bias, R, ldr, Y, ldy, M, N, K, lfv);
-    else
-      hipLaunchKernelGGL((gemm_pipe_kernel<EPI_BIAS_F16, true, 4>), grid, block, 0, stream, X, lda,
-                         W, bias, R, ldr, Y, ldy, M, N, K, lfv);
-  } else if (v == GEMM_DIAG_NOLOAD || v == GEMM_DIAG_NOEPI) {
-    const dim3 grid((unsigned)big_tiles), block(512);
-    if (v == GEMM_DIAG_NOLOAD)
-      hipLaunchKernelGGL((gemm_pipe_kernel<EPI_BIAS_F16, false, 1>), grid, block, 0, stream, X, lda,
-                         W, bias, R, ldr, Y, ldy, M, N, K, lfv);
-    else
-      hipLaunchKernelGGL((gemm_pipe_kernel<EPI_BIAS_F16, false, 2>), grid, block, 0, stream, X, lda,
-                         W, bias, R, ldr, Y, ldy, M, N, K, lfv);
+    case FAM_PIPE_DIAG: {  // timing only: EPI_BIAS_F16 kernels whatever the epilogue
+      auto kern = gemm_pipe_kernel<EPI_BIAS_F16, true, 2>;  // GEMM_DIAG_P_NOEPI
+      if (p.variant == GEMM_DIAG_P_MATHONLY) kern = gemm_pipe_kernel<EPI_BIAS_F16, true, 3>;
+      if (p.variant == GEMM_DIAG_P_STOREONLY) kern = gemm_pipe_kernel<EPI_BIAS_F16, true, 4>;
+      if (p.variant == GEMM_DIAG_NOLOAD) kern = gemm_pipe_kernel<EPI_BIAS_F16, false, 1>;
+      if (p.variant == GEMM_DIAG_NOEPI) kern = gemm_pipe_kernel<EPI_BIAS_F16, false, 2>;
+      hipLaunchKernelGGL(kern, dim3(p.grid_x), dim3(p.block), 0, stream, X, lda, W, bias, R, ldr, Y, ldy, M, N,
+                         K, lfv);
+      break;
+    }
 #endif
-  } else if (v == GEMM_PP) {
-    const int64_t tiles = (int64_t)(N / 256) * ceil_div(M, 128);
-    const dim3 grid((unsigned)tiles), block(256);
+    case FAM_PP:
 #define SR_PP_CASE(E)                                                                            \
   case E:                                                                                        \
-    hipLaunchKernelGGL((gemm_pp_kernel<E>), grid, block, 0, stream, X, lda, W, bias, R, ldr, Y,  \
-                       ldy, M, N, K, lfv);                                                       \
+    static_assert(epi_traits(E).pp, "pp family");                                                \
+    hipLaunchKernelGGL((gemm_pp_kernel<E>), dim3(p.grid_x), dim3(p.block), 0, stream, X, lda, W, \
+                       bias, R, ldr, Y, ldy, M, N, K, lfv);                                      \
     break;
-    switch (epi) {
-      SR_PP_CASE(EPI_BIAS_F16)
-      SR_PP_CASE(EPI_BIAS_GELU_F16)
-      SR_PP_CASE(EPI_BIAS_RES_F32)
-      SR_PP_CASE(EPI_BIAS_RES_F16)
-      SR_PP_CASE(EPI_BIAS_TANH_F32)
-      SR_PP_CASE(EPI_LNF_F16)
-      SR_PP_CASE(EPI_LNF_GELU_F16)
-      SR_PP_CASE(EPI_RES16_STATS)
-      SR_PP_CASE(EPI_LNR16_STATS)
-      default: SR_CHECK(false, "gemm: unknown epilogue");
-    }
+      switch (epi) {
+        SR_PP_CASE(EPI_BIAS_F16)
+        SR_PP_CASE(EPI_BIAS_GELU_F16)
+        SR_PP_CASE(EPI_BIAS_RES_F32)
+        SR_PP_CASE(EPI_BIAS_RES_F16)
+        SR_PP_CASE(EPI_BIAS_TANH_F32)
+        SR_PP_CASE(EPI_LNF_F16)
+        SR_PP_CASE(EPI_LNF_GELU_F16)
+        SR_PP_CASE(EPI_RES16_STATS)
+        SR_PP_CASE(EPI_LNR16_STATS)
+        default: SR_CHECK(false, "gemm: unknown epilogue");
+      }
 #undef SR_PP_CASE
-  } else if (v == GEMM_PIPE || v == GEMM_PIPE_PERSIST) {
-    // (the FFN1 epilogues stage their constants during K-step 1 of a persistent tile: nk >= 4)
-    // (the persistent LNR epilogues stage consecutive row statistics: stat_ld 1)
-    const bool persist = v == GEMM_PIPE_PERSIST && K >= 2 * GBK &&
-                         ((epi != EPI_LNF_GELU_F16 && epi != EPI_LNF_GELU_F8) || K >= 4 * GBK) &&
-                         !(epi == EPI_LNR16_STATS && lfv.stat_ld != 1);
-    // persistent: 8 XCD groups x G walkers (one 8-wave workgroup per CU, 128 KiB LDS)
-    const int64_t g = persist ? 8 * std::min<int64_t>(32, ceil_div(big_tiles, 8)) : big_tiles;
-    SR_CHECK(!persist || (g % 8 == 0 && g >= 8), "gemm: persistent grid must be a multiple of 8");
-    const dim3 grid((unsigned)g), block(512);
-#define SR_PIPE_CASE(E)                                                                          \
-  case E:                                                                                        \
-    if (persist)                                                                                 \
-      hipLaunchKernelGGL((gemm_pipe_kernel<E, true>), grid, block, 0, stream, X, lda, W, bias, R, \
-                         ldr, Y, ldy, M, N, K, lfv);                                             \
-    else                                                                                         \
-      hipLaunchKernelGGL((gemm_pipe_kernel<E, false>), grid, block, 0, stream, X, lda, W, bias, R,\
-                         ldr, Y, ldy, M, N, K, lfv);                                             \
-    break;
-    switch (epi) {
-      SR_PIPE_CASE(EPI_BIAS_F16)
-      SR_PIPE_CASE(EPI_BIAS_GELU_F16)
-      SR_PIPE_CASE(EPI_BIAS_RES_F32)
-      SR_PIPE_CASE(EPI_BIAS_RES_F16)
-      SR_PIPE_CASE(EPI_BIAS_TANH_F32)
-      SR_PIPE_CASE(EPI_LNF_F16)
-      SR_PIPE_CASE(EPI_LNF_GELU_F16)
-      SR_PIPE_CASE(EPI_RES16_STATS)
-      SR_PIPE_CASE(EPI_LNR16_STATS)
-      SR_PIPE_CASE(EPI_LNF_GELU_F8)
-      SR_PIPE_CASE(EPI_RES16_STATS_Y8)
-      SR_PIPE_CASE(EPI_LNR16_STATS_Y8)
-      default: SR_CHECK(false, "gemm: unknown epilogue");
-    }
-#undef SR_PIPE_CASE
-  } else {
-    const int64_t tiles = (int64_t)(N / 128) * ceil_div(M, 128);
-    SR_CHECK(tiles < (1ll << 31), "gemm: too many tiles");
-    // split-K over the K chunks (see KCHUNK) when the tiles alone leave the CUs idle and the
-    // caller lent a workspace for the partial tiles (64 KiB per tile and chunk): chunk groups of
-    // cpg chunks, about 512 workgroups in all
-    const int64_t nchunk = ceil_div(K / GBK, KCHUNK);
-    int64_t groups = 1, cpg = 0;
-    if (lf && lf->chunk_ws && nchunk >= 2 && tiles <= kSplitMaxTiles &&
-        nchunk * tiles * 65536 <= lf->chunk_ws_bytes) {
-      cpg = ceil_div(nchunk, std::min<int64_t>(nchunk, ceil_div(512, tiles)));
-      groups = ceil_div(nchunk, cpg);
-    }
-    // (chunked sums only for the callers that lent a workspace: the same chunks split or not)
-    launch_tile<128, 128, 2, 2, false>(epi, dim3((unsigned)tiles, (unsigned)groups), stream, X, lda, W,
-                                       bias, R, ldr, Y, ldy, M, N, K, x_k / GBK,
-                                       cpg ? reinterpret_cast<float4v*>(lf->chunk_ws) : nullptr, (int)cpg,
-                                       lf && lf->chunk_ws ? KCHUNK : 0);
+      break;
+    case FAM_PIPE:
+#define SR_F16_CASE(E) SR_PIPE_CASE(E, false, pipe, X, lda, W, K, lfv)
+      switch (epi) {
+        SR_F16_CASE(EPI_BIAS_F16)
+        SR_F16_CASE(EPI_BIAS_GELU_F16)
+        SR_F16_CASE(EPI_BIAS_RES_F32)
+        SR_F16_CASE(EPI_BIAS_RES_F16)
+        SR_F16_CASE(EPI_BIAS_TANH_F32)
+        SR_F16_CASE(EPI_LNF_F16)
+        SR_F16_CASE(EPI_LNF_GELU_F16)
+        SR_F16_CASE(EPI_RES16_STATS)
+        SR_F16_CASE(EPI_LNR16_STATS)
+        SR_F16_CASE(EPI_LNF_GELU_F8)
+        SR_F16_CASE(EPI_RES16_STATS_Y8)
+        SR_F16_CASE(EPI_LNR16_STATS_Y8)
+        default: SR_CHECK(false, "gemm: unknown epilogue");
+      }
+#undef SR_F16_CASE
+      break;
+    default:  // FAM_TILE128
+      launch_tile<128, 128, 2, 2>(p, epi, stream, X, lda, W, bias, R, ldr, Y, ldy, M, N, K,
+                                  p.cpg ? reinterpret_cast<float4v*>(lf->chunk_ws) : nullptr);
   }
+#undef SR_PIPE_CASE
   SR_LAUNCH_CHECK();
 }
 

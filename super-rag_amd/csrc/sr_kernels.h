@@ -2,36 +2,9 @@
 #pragma once
 
 #include "sr_common.h"
+#include "sr_gemm_plan.h"  // Epilogue, GemmVariant
 
 namespace sr {
-
-enum Epilogue {
-  EPI_BIAS_F16 = 0,       // y = acc + b                 -> fp16
-  EPI_BIAS_GELU_F16 = 1,  // y = gelu_erf(acc + b)       -> fp16
-  EPI_BIAS_RES_F32 = 2,   // y = acc + b + R (fp32)      -> fp32
-  EPI_BIAS_TANH_F32 = 3,  // y = tanh(acc + b)           -> fp32 (classifier head)
-  EPI_BIAS_RES_F16 = 4,   // y = acc + b + R (fp16)      -> fp16
-  // LayerNorm folded into the GEMMs around it (fp16 residual stream; pipelined 256x256 kernels,
-  // N % 256 == 0).  The A operand / residual is the UN-normalised row u with LN(u) =
-  // (u - mu) * rstd * gamma + beta; mu / rstd come from per-row partial statistics written by the
-  // producing GEMM's epilogue (LnFold below).
-  EPI_LNF_F16 = 5,        // y = rstd * (acc - mu * c[n]) + b'[n], W' = W . diag(gamma) -> fp16
-  EPI_LNF_GELU_F16 = 6,   // y = 2 gelu(same) (the FFN2 weight carries the 0.5)          -> fp16
-  EPI_RES16_STATS = 7,    // y = acc + b + R (fp16, already normalised) -> fp16 + row statistics
-  EPI_LNR16_STATS = 8,    // y = acc + b + LN(R) (R un-normalised)      -> fp16 + row statistics
-  // K1 on the GEMM main loop (internal: launch_cosine_scan_gemm): W = corpus rows, X = queries,
-  // epilogue = threshold filter appending (sim, row) keys to per-query candidate lists
-  EPI_SCAN = 9,
-  // the same on OCP fp8-e4m3 operands e4m3(256 x) of unit vectors (block-scaled MFMA
-  // v_mfma_scale_f32_16x16x128_f8f6f4, E8M0 block scales 2^-8 undo the factor)
-  EPI_SCAN8 = 10,
-  // EPI_LNF_GELU_F16 storing OCP e4m3(2 GELU) bytes (the fp8 FFN1; its consumer runs fp8)
-  EPI_LNF_GELU_F8 = 11,
-  // EPI_RES16_STATS / EPI_LNR16_STATS that also store an e4m3 copy of their fp16 output to
-  // LnFold.y8 (the next fp8 GEMM's A operand; separate codes keep the fp16 kernels' registers)
-  EPI_RES16_STATS_Y8 = 12,
-  EPI_LNR16_STATS_Y8 = 13
-};
 
 // Per-row statistics hand-over between GEMMs (Chan-combinable partials over 128-column spans):
 // stat[row][part] = (sum, M2 = sum (x - sum/128)^2) of the fp16-rounded outputs in that span.
@@ -56,7 +29,7 @@ struct LnFold {
                                    // past x_k re-read X from k = 0, so W = [W_hi | W_lo] (N x 2 x_k)
                                    // gives X W_hi^T + X W_lo^T in one fp32 accumulation (0 = K)
   float* chunk_ws = nullptr;        // GEMM_SMALL (128 x 128, short M): workspace for split-K
-  int64_t chunk_ws_bytes = 0;      // partial tiles (k_gemm.hip KCHUNK); null: never split
+  int64_t chunk_ws_bytes = 0;      // partial tiles (sr_gemm_plan.h KCHUNK); null: never split
   // EPI_SCAN(8) re-uses the fields (kernel-argument SGPRs are scarce in the persistent kernels):
   // stat_out = per-query candidate counts (int*), stat_ld = global row id of the chunk's first
   // row; bias = tau[B], R = live flags of the chunk, Y = candidate keys [B][cap] (ldy = cap).
@@ -66,9 +39,6 @@ struct LnFold {
 void launch_gemm(int epi, const half_t* X, int64_t lda, const half_t* W, const float* bias,
                  const void* R, int64_t ldr, void* Y, int64_t ldy, int M, int N, int K,
                  hipStream_t stream, const LnFold* lf = nullptr);
-enum GemmVariant { GEMM_SMALL = 0, GEMM_BIG = 1, GEMM_PIPE = 4, GEMM_PIPE_PERSIST = 5,
-                   GEMM_DIAG_NOLOAD = 6, GEMM_DIAG_NOEPI = 7 /* timing only */, GEMM_PP = 8,
-                   GEMM_DIAG_P_NOEPI = 9, GEMM_DIAG_P_MATHONLY = 10, GEMM_DIAG_P_STOREONLY = 11 };
 void launch_gemm_variant(int variant, int epi, const half_t* X, int64_t lda, const half_t* W,
                          const float* bias, const void* R, int64_t ldr, void* Y, int64_t ldy,
                          int M, int N, int K, hipStream_t stream, const LnFold* lf = nullptr);
