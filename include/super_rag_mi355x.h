@@ -473,9 +473,36 @@ int sr_lex_score_rows_weighted(sr_lex* x, const int64_t* qoff, const int32_t* qt
  *                   implies (truncated, or a trailing byte), off[0] != 0, decreasing offsets, a row of
  *                   2^31 tokens or more, off[n_rows] != n_tokens, a live byte above 1, an e4m3 NaN code
  *                   (0x7f, 0xff) in an fp8 pool.
- * Not provided: a multi-device variant, shrinking the pool, a whole-corpus MaxSim scan,
- * per-token scales or residual codecs, quantised queries, a fused rerank entry point
- * (multivec.m3_rerank composes the existing ones).
+ * Whole-corpus search (k_mvscan.hip; DESIGN.md "Whole-corpus MaxSim search"): the index as a first
+ * stage of its own, exact, one pass over the pool per group of queries.
+ *   sr_mv_search_dev  q fp16 [B, ld_q, dim], q_len int32 [B], allow n_rows bytes or NULL, out_score
+ *                   fp32 [B, k], out_rows int64 [B, k], all device.  For query b the k eligible rows
+ *                   with the highest MaxSim, ordered by (score desc, row asc), the store's tie rule.  A
+ *                   row is eligible when it is live, holds at least one token and, where allow is
+ *                   given, allow[row] != 0.  Slots past the eligible rows hold -inf / -1; a query with
+ *                   q_len[b] == 0 gets -inf / -1 in every slot; so does every query on an empty index.
+ *                   row_offset is added to every real row.  Asynchronous on `stream` after its
+ *                   host-side planning; nothing is read back.
+ *   sr_mv_search    the same on host buffers: q fp32 rounded to nearest fp16, allow n_rows host bytes
+ *                   or NULL, uploaded per call (no key cache), no row_offset.  Blocking.
+ *   sr_mv_search_group  the queries of one workgroup of the scan at `dim` (the Q below): 3 up to dim
+ *                   384, 2 up to 512, 1 above.  Needs no device.
+ * Score bits: out_score for (b, row) equals what sr_mv_score_rows / _dev returns for the same pair,
+ * bit for bit, on both pool dtypes: a pair's bits depend on the pair alone here too, not on B, k, allow,
+ * slab_rows or the other rows.  The query rows at and past q_len[b] are never read; the device variant
+ * clamps q_len as sr_mv_score_rows_dev does, the host variant checks it.  Token values are finite by
+ * contract; the place of a NaN score in the list is unspecified, but nothing is indexed by it.
+ * Memory: the scan works in slabs of at most slab_rows consecutive rows; 0 means as many rows as keep
+ * the per-slab score scratch B * rows * 4 bytes within 64 MiB, at least 1024.  The extra device memory
+ * is that scratch plus a running list of B * k 64-bit keys, kept by the index between calls: never
+ * O(B * n_rows), never O(number of slabs).  The result does not depend on slab_rows, in bits.
+ * Limits, SR_ERR_INVALID before any device work: a NULL handle; k outside [1, SR_MAX_TOPK]; ld_q < 1;
+ * B < 0; slab_rows < 0; row_offset < 0; a null buffer (allow excepted); q_len[b] outside [0, min(ld_q,
+ * SR_MV_MAX_QUERY_TOKENS)] on the host variant.  B == 0 is a no-op.
+ * Not provided: a multi-device variant, shrinking the pool, per-token scales or residual codecs,
+ * quantised queries, a fused rerank entry point (multivec.m3_rerank composes the existing ones); for
+ * the search: an allow key cache, grouped, MMR or subset variants, approximate pruning (centroids,
+ * PLAID), a connector ctx switch.
  * ---------------------------------------------------------------------------------------------- */
 #define SR_MV_MAX_QUERY_TOKENS 512
 typedef struct sr_mv sr_mv;
@@ -493,6 +520,12 @@ int sr_mv_score_rows_dev(sr_mv* x, const void* q, const int32_t* q_len, int B, i
                          const int64_t* rows, int K, float* out_score, void* stream);
 int sr_mv_score_rows(sr_mv* x, const float* q, const int32_t* q_len, int B, int ld_q,
                      const int64_t* rows, int K, float* out_score);
+int sr_mv_search(sr_mv* x, const float* q, const int32_t* q_len, int B, int ld_q, int k,
+                 const uint8_t* allow, int64_t slab_rows, float* out_score, int64_t* out_rows);
+int sr_mv_search_dev(sr_mv* x, const void* q, const int32_t* q_len, int B, int ld_q, int k,
+                     const uint8_t* allow, int64_t slab_rows, int64_t row_offset,
+                     float* out_score, int64_t* out_rows, void* stream);
+int sr_mv_search_group(int dim, int* queries);
 int sr_mv_dim(sr_mv* x, int* dim);
 int sr_mv_compact(sr_mv* x, int64_t stage_bytes, int64_t* old_to_new);
 int sr_mv_save(sr_mv* x, const char* path);

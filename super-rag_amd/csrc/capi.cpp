@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "sr_kernels.h"
+#include "sr_mv_plan.h"
 #include "sr_runtime.h"
 
 struct sr_store {
@@ -1335,6 +1336,35 @@ int sr_mv_score_rows(sr_mv* x, const float* q, const int32_t* q_len, int B, int 
   SR_NONNULL(x);
   std::lock_guard<std::mutex> lk(x->impl->mu);
   x->impl->score_rows_host(q, q_len, B, ld_q, rows, K, out_score);
+  SR_API_END
+}
+
+int sr_mv_search(sr_mv* x, const float* q, const int32_t* q_len, int B, int ld_q, int k,
+                 const uint8_t* allow, int64_t slab_rows, float* out_score, int64_t* out_rows) {
+  SR_API_BEGIN
+  SR_NONNULL(x);
+  std::lock_guard<std::mutex> lk(x->impl->mu);
+  x->impl->search_host(q, q_len, B, ld_q, k, allow, slab_rows, out_score, out_rows);
+  SR_API_END
+}
+
+int sr_mv_search_dev(sr_mv* x, const void* q, const int32_t* q_len, int B, int ld_q, int k,
+                     const uint8_t* allow, int64_t slab_rows, int64_t row_offset, float* out_score,
+                     int64_t* out_rows, void* stream) {
+  SR_API_BEGIN
+  SR_NONNULL(x);
+  std::lock_guard<std::mutex> lk(x->impl->mu);
+  x->impl->search_dev(reinterpret_cast<const sr::half_t*>(q), q_len, B, ld_q, k, allow, slab_rows, row_offset,
+                      out_score, out_rows, reinterpret_cast<hipStream_t>(stream));
+  SR_API_END
+}
+
+int sr_mv_search_group(int dim, int* queries) {
+  SR_API_BEGIN
+  SR_NONNULL(queries);
+  if (dim < 64 || dim > 1024 || dim % 64 != 0)
+    throw sr::Error(SR_ERR_INVALID, "mv: dim must be a multiple of 64, <= 1024");
+  *queries = sr::mv_group_queries(dim);
   SR_API_END
 }
 

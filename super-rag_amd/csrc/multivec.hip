@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "sr_kernels.h"
+#include "sr_mv_plan.h"
 #include "sr_runtime.h"
 
 namespace sr {
@@ -265,6 +266,90 @@ void MultiVecIndex::score_rows_host(const float* q, const int32_t* q_len, int B,
   SR_HIP(hipMemcpyAsync(drows, rows, no * sizeof(int64_t), hipMemcpyHostToDevice, stream_));
   score_rows_dev(dq, dlen, B, ld_q, drows, K, dout, stream_);
   SR_HIP(hipMemcpyAsync(out, dout, no * sizeof(float), hipMemcpyDeviceToHost, stream_));
+  SR_HIP(hipStreamSynchronize(stream_));
+}
+
+// ---- whole-corpus search ---------------------------------------------------------------------------
+// The rows in slabs (sr_mv_plan.h): per slab one scan launch (k_mvscan.hip) into the score scratch
+// [B][slab rows] and one selection launch that folds the slab into the running [B, k] list; the last
+// selection writes the caller's outputs.  Planning needs the offsets' host mirror only (the tokens of a
+// slab size its grid), so nothing is read back.  scan_ holds the scratch and the list; calls on the
+// index are ordered by the completion event, so one buffer serves them all.
+static void search_check_args(int B, int ld_q, int k, int64_t slab_rows, int64_t row_offset) {
+  SR_CHECK(B >= 0, "mv.search: negative batch");
+  SR_CHECK(k >= 1 && k <= SR_MAX_TOPK, "mv.search: k must be in [1, 1024]");
+  SR_CHECK(ld_q >= 1, "mv.search: ld_q must be >= 1");
+  SR_CHECK(slab_rows >= 0, "mv.search: slab_rows must be >= 0 (0: the default)");
+  SR_CHECK(row_offset >= 0, "mv.search: row_offset must be >= 0");
+}
+
+void MultiVecIndex::search_dev(const half_t* q, const int32_t* q_len, int B, int ld_q, int k,
+                               const uint8_t* allow, int64_t slab_rows, int64_t row_offset, float* out_score,
+                               int64_t* out_rows, hipStream_t s) {
+  search_check_args(B, ld_q, k, slab_rows, row_offset);
+  if (B == 0) return;
+  SR_CHECK(q && q_len && out_score && out_rows, "mv.search: null buffer");
+  SR_CHECK(n_rows_ < 0xffffffffll, "mv.search: the index holds too many rows for a 32-bit key");
+  const int64_t slab = std::min(mv_slab_rows(slab_rows, B), std::max<int64_t>(n_rows_, 1));
+  DeviceGuard g(device_);
+  float* score;
+  uint64_t* run_keys;
+  int* run_n;
+  Carve c;
+  c.part((size_t)B * (size_t)slab, &score);
+  c.part((size_t)B * k, &run_keys);
+  c.part((size_t)B, &run_n);
+  scan_.carve(c);
+  begin(s);
+  const int64_t ns = mv_slab_count(n_rows_, slab);
+  for (int64_t i = 0; i < ns; ++i) {
+    int64_t r0, r1;
+    mv_slab(n_rows_, slab, i, &r0, &r1);
+    launch_maxsim_scan(pool_.p, dtype_, off_.as<int64_t>(), live_.as<uint8_t>(), allow, dim_, q, q_len, B, ld_q,
+                       r0, r1, off_host_[(size_t)r0], off_host_[(size_t)r1], score, slab, s);
+    launch_mv_topk(score, slab, r0, r1 - r0, B, k, i == 0, i == ns - 1, run_keys, run_n, out_score, out_rows,
+                   row_offset, s);
+  }
+  if (ns == 0)  // an empty index: -inf / -1
+    launch_mv_topk(score, slab, 0, 0, B, k, true, true, run_keys, run_n, out_score, out_rows, row_offset, s);
+  end(s);
+}
+
+void MultiVecIndex::search_host(const float* q, const int32_t* q_len, int B, int ld_q, int k,
+                                const uint8_t* allow, int64_t slab_rows, float* out_score, int64_t* out_rows) {
+  search_check_args(B, ld_q, k, slab_rows, 0);
+  if (B == 0) return;
+  SR_CHECK(q && q_len && out_score && out_rows, "mv.search: null buffer");
+  for (int b = 0; b < B; ++b)
+    SR_CHECK(q_len[b] >= 0 && q_len[b] <= SR_MV_MAX_QUERY_TOKENS && q_len[b] <= ld_q,
+             "mv.search: q_len must be in [0, min(ld_q, 512)]");
+  DeviceGuard g(device_);
+  const size_t nq = (size_t)B * ld_q * dim_, no = (size_t)B * k;
+  float *dq32, *dscore;
+  half_t* dq;
+  int32_t* dlen;
+  uint8_t* dallow;
+  int64_t* drows;
+  Carve c;
+  c.part(nq, &dq32, &dq);
+  c.part((size_t)B, &dlen);
+  c.part(allow ? (size_t)n_rows_ : 0, &dallow);
+  c.part(no, &dscore, &drows);
+  hostio_.carve(c);
+  begin(stream_);
+  // only the rows below q_len travel: the rest of the caller's buffer is never read
+  SR_HIP(hipMemsetAsync(dq32, 0, nq * sizeof(float), stream_));
+  for (int b = 0; b < B; ++b)
+    if (q_len[b] > 0)
+      SR_HIP(hipMemcpyAsync(dq32 + (size_t)b * ld_q * dim_, q + (size_t)b * ld_q * dim_,
+                            (size_t)q_len[b] * dim_ * sizeof(float), hipMemcpyHostToDevice, stream_));
+  launch_convert_f32_f16(dq32, dq, (int64_t)nq, stream_);
+  SR_HIP(hipMemcpyAsync(dlen, q_len, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+  if (allow && n_rows_ > 0)
+    SR_HIP(hipMemcpyAsync(dallow, allow, (size_t)n_rows_, hipMemcpyHostToDevice, stream_));
+  search_dev(dq, dlen, B, ld_q, k, allow ? dallow : nullptr, slab_rows, 0, dscore, drows, stream_);
+  SR_HIP(hipMemcpyAsync(out_score, dscore, no * sizeof(float), hipMemcpyDeviceToHost, stream_));
+  SR_HIP(hipMemcpyAsync(out_rows, drows, no * sizeof(int64_t), hipMemcpyDeviceToHost, stream_));
   SR_HIP(hipStreamSynchronize(stream_));
 }
 

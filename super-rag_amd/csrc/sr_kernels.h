@@ -264,6 +264,19 @@ void maxsim_check_args(int dim, int B, int ld_q, int K);
 void launch_maxsim(const void* pool, int dtype, const int64_t* off, const uint8_t* live, int64_t n_rows,
                    int dim, const half_t* q, const int32_t* q_len, int B, int ld_q,
                    const int64_t* rows, int K, float* out, double tokens_hint, hipStream_t s);
+// K9s (k_mvscan.hip, plan in sr_mv_plan.h): MaxSim of every query against the rows [row0, row1) of the
+// pool (tokens [T0, T1)) into score [B][ld_s], column row - row0, bit for bit launch_maxsim's value of
+// the pair; -inf for a row that is dead, empty or not allowed (allow [n_rows] bytes, may be null) and for
+// an empty query.  launch_mv_topk folds the slab's scores into the running list run_keys [B][k] /
+// run_n [B] (`first`: the list starts empty) and, on the `last` slab, writes out_score / out_rows [B][k]
+// ordered (score desc, row asc), -inf / -1 past the eligible rows, row_offset added to the rows.
+void launch_maxsim_scan(const void* pool, int dtype, const int64_t* off, const uint8_t* live,
+                        const uint8_t* allow, int dim, const half_t* q, const int32_t* q_len, int B, int ld_q,
+                        int64_t row0, int64_t row1, int64_t T0, int64_t T1, float* score, int64_t ld_s,
+                        hipStream_t s);
+void launch_mv_topk(const float* score, int64_t ld_s, int64_t row0, int64_t nrows, int B, int k, bool first,
+                    bool last, uint64_t* run_keys, int* run_n, float* out_score, int64_t* out_rows,
+                    int64_t row_offset, hipStream_t s);
 void launch_mv_pack(const half_t* src, const int64_t* off, int64_t n, int ld_tok, int dim,
                     half_t* pool, hipStream_t s);
 void launch_mv_pack_fp8(const half_t* src, const int64_t* off, int64_t n, int64_t ld_tok, int dim,

@@ -510,6 +510,14 @@ class MultiVecIndex {
                       int K, float* out, hipStream_t s);
   void score_rows_host(const float* q, const int32_t* q_len, int B, int ld_q, const int64_t* rows,
                        int K, float* out);
+  // the k eligible rows (live, not empty, allow[row] != 0 where allow is given) with the highest
+  // MaxSim per query, (score desc, row asc), -inf / -1 past them; the scan runs in slabs of at most
+  // slab_rows rows (0: sr_mv_plan.h's default).  Device buffers, asynchronous on s, nothing read back.
+  void search_dev(const half_t* q, const int32_t* q_len, int B, int ld_q, int k, const uint8_t* allow,
+                  int64_t slab_rows, int64_t row_offset, float* out_score, int64_t* out_rows, hipStream_t s);
+  // the same on host buffers (allow: n_rows bytes or null).  Blocking.
+  void search_host(const float* q, const int32_t* q_len, int B, int ld_q, int k, const uint8_t* allow,
+                   int64_t slab_rows, float* out_score, int64_t* out_rows);
   // drops the tombstoned rows in place (kept rows keep their order; capacities stay): the kept
   // tokens move down the pool in chunks, through at most stage_bytes of staging (0: the default);
   // old_to_new (n_rows entries, may be null) as Store::compact writes it
@@ -538,6 +546,7 @@ class MultiVecIndex {
   hipEvent_t done_ = nullptr;
   int64_t n_rows_ = 0, n_live_ = 0, n_tokens_ = 0, cap_rows_ = 0, cap_tokens_ = 0;
   DevBuf pool_, off_, live_, hostio_;
+  DevBuf scan_;  // search: one slab's score scratch and the running [B, k] list
   std::vector<int64_t> off_host_{0};   // n_rows_ + 1 entries
   std::vector<uint8_t> live_host_;
 };

@@ -214,6 +214,11 @@ SIGNATURES = {
     "sr_mv_score_rows_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p,
                                      c_void_p]),
     "sr_mv_score_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "sr_mv_search": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p,
+                             c_void_p]),
+    "sr_mv_search_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_int64,
+                                 c_void_p, c_void_p, c_void_p]),
+    "sr_mv_search_group": (c_int, [c_int, POINTER(c_int)]),
     "sr_mv_dim": (c_int, [c_void_p, POINTER(c_int)]),
     "sr_mv_compact": (c_int, [c_void_p, c_int64, c_void_p]),
     "sr_mv_save": (c_int, [c_void_p, c_char_p]),

@@ -200,6 +200,87 @@ class NativeMultiVectorIndex:
                    K, N.ptr(out), N.stream_handle(stream))
         return out
 
+    def _padded(self, q_vecs, q_len, what):
+        """(q [B, ld_q, dim] fp32, q_len [B] int32) of score_rows' / search's two query conventions."""
+        if q_len is None:
+            return pad_queries(q_vecs, self.dim)
+        q = np.ascontiguousarray(np.asarray(q_vecs, dtype=np.float32))
+        qlen = np.ascontiguousarray(np.asarray(q_len, dtype=np.int32).reshape(-1))
+        if q.ndim != 3 or q.shape[2] != self.dim or q.shape[0] != qlen.size:
+            raise ValueError(f"{what}: padded queries must be [{qlen.size}, ld_q, {self.dim}], got {q.shape}")
+        return q, qlen
+
+    def _allow_bytes(self, allow):
+        """allow -> uint8 [rows] (non-zero: the row may be returned), ValueError on another length."""
+        a = np.ascontiguousarray(np.asarray(allow).reshape(-1) != 0).astype(np.uint8)
+        n = self.stats()["rows"]
+        if a.size != n:
+            raise ValueError(f"allow must have one entry per row ({n}), got {a.size}")
+        return a
+
+    def search(self, q_vecs, k: int, q_len=None, allow=None, slab_rows: int = 0):
+        """Exact MaxSim top-k over the whole index (sr_mv_search): for every query the k eligible rows
+        (live, at least one token, allow[row] != 0 where ``allow`` [rows] is given) with the highest
+        MaxSim -> (score [B, k] fp32, rows [B, k] int64), ordered (score desc, row asc), -inf / -1 past
+        the eligible rows and for an empty query.  Every score is score_rows' value of the pair, bit
+        for bit.  q_vecs / q_len as for score_rows.  ``slab_rows`` bounds the rows scanned per pass
+        (0: the default, 64 MiB of score scratch); the result does not depend on it."""
+        q, qlen = self._padded(q_vecs, q_len, "search")
+        a = None if allow is None else self._allow_bytes(allow)
+        B = q.shape[0]
+        score = np.empty((B, max(int(k), 0)), dtype=np.float32)
+        rows = np.empty((B, max(int(k), 0)), dtype=np.int64)
+        N.call("sr_mv_search", self._h, N.ptr(q), N.ptr(qlen), B, q.shape[1], int(k),
+               None if a is None or a.size == 0 else N.ptr(a), int(slab_rows), N.ptr(score), N.ptr(rows))
+        return score, rows
+
+    def search_dev(self, q, q_len, k: int, allow=None, row_offset: int = 0, slab_rows: int = 0, out=None,
+                   stream=None):
+        """search on device tensors (sr_mv_search_dev), asynchronous on ``stream``: q fp16 [B, ld_q,
+        dim], q_len int32 [B], allow uint8 / bool [rows] or None -> (score fp32 [B, k], rows int64
+        [B, k]); ``row_offset`` is added to every real row; ``out`` may give the two output tensors.
+
+        NOTE: unlike search, this call cannot inspect ``q_len`` (it lives on the device and a check
+        would synchronise the stream), so it raises nothing for a bad length: q_len[b] is CLAMPED to
+        [0, min(ld_q, 512)].  A caller that passes q_len[b] > ld_q or > 512 gets the MaxSim over the
+        first min(ld_q, 512) query tokens only, a plausible but different ranking, and no error;
+        q_len[b] <= 0 gives -inf / -1.  Keep q_len within the padded rows."""
+        import torch
+        if not (q.is_cuda and q.is_contiguous() and q.dtype == torch.float16 and q.dim() == 3
+                and q.shape[2] == self.dim):
+            raise ValueError(f"search_dev: contiguous fp16 device queries [B, ld_q, {self.dim}]")
+        if not (q_len.is_cuda and q_len.is_contiguous() and q_len.dtype == torch.int32
+                and q_len.shape == (q.shape[0],)):
+            raise ValueError("search_dev: q_len int32 [B] on the device")
+        if allow is not None:
+            if not (allow.is_cuda and allow.is_contiguous() and allow.dtype in (torch.uint8, torch.bool)
+                    and allow.dim() == 1):
+                raise ValueError("search_dev: allow must be a contiguous uint8 / bool device tensor [rows]")
+            n = self.stats()["rows"]
+            if allow.numel() != n:
+                raise ValueError(f"allow must have one entry per row ({n}), got {allow.numel()}")
+        B, k = int(q.shape[0]), int(k)
+        if out is None:
+            out = (torch.empty((B, max(k, 0)), dtype=torch.float32, device=q.device),
+                   torch.empty((B, max(k, 0)), dtype=torch.int64, device=q.device))
+        score, rows = out
+        if not (score.is_cuda and score.is_contiguous() and score.dtype == torch.float32
+                and rows.is_cuda and rows.is_contiguous() and rows.dtype == torch.int64
+                and tuple(score.shape) == (B, k) and tuple(rows.shape) == (B, k)):
+            raise ValueError(f"search_dev: out must be (fp32 [{B}, {k}], int64 [{B}, {k}]) on the device")
+        N.call("sr_mv_search_dev", self._h, N.ptr(q), N.ptr(q_len), B, int(q.shape[1]), k,
+               None if allow is None or allow.numel() == 0 else N.ptr(allow), int(slab_rows), int(row_offset),
+               N.ptr(score), N.ptr(rows), N.stream_handle(stream))
+        return score, rows
+
+
+def search_group_queries(dim: int) -> int:
+    """Queries one workgroup of the whole-corpus scan shares a document tile among at ``dim``
+    (sr_mv_search_group; needs no device)."""
+    q = ctypes.c_int(0)
+    N.call("sr_mv_search_group", int(dim), ctypes.byref(q))
+    return int(q.value)
+
 
 def _rows_live(part):
     """(rows, live) of a store (count()) or of a row-aligned index (stats())."""
@@ -305,11 +386,15 @@ def m3_rerank(store, mv: NativeMultiVectorIndex, q_dense, q_vecs, cand_rows, k: 
 
 def m3_search(store, mv: NativeMultiVectorIndex, q_dense, q_vecs, k: int, k_cand: Optional[int] = None,
               impact=None, q_sparse=None, weights=(1, 1, 1), fusion: str = "rrf", allow=None,
-              mask_key: int = 0):
+              mask_key: int = 0, first_stage: str = "dense"):
     """First stage + m3_rerank: the k_cand (default 4 k) candidates of lexical.sparse_hybrid_search
     (dense + learned sparse, ``fusion`` as there) or, without an impact index, of store.search_sim,
     reranked by the combined score.  k <= k_cand <= 1024 (sr_mv_score_rows' limit on the candidates
-    of one query); the default is clamped to it."""
+    of one query); the default is clamped to it.  ``first_stage="multivec"`` takes the candidates
+    from the exact MaxSim scan ``mv.search(q_vecs, k_cand, allow=allow)`` instead (``mask_key`` is
+    unused there), so a passage only late interaction finds can reach the rerank."""
+    if first_stage not in ("dense", "multivec"):
+        raise ValueError(f'first_stage must be "dense" or "multivec", got {first_stage!r}')
     k = int(k)
     if not 1 <= k <= N.SR_MAX_TOPK:
         raise ValueError(f"k must be in [1, {N.SR_MAX_TOPK}], got {k}")
@@ -320,7 +405,9 @@ def m3_search(store, mv: NativeMultiVectorIndex, q_dense, q_vecs, k: int, k_cand
     qd = np.ascontiguousarray(np.asarray(q_dense, dtype=np.float32))
     if qd.ndim == 1:
         qd = qd[None]
-    if impact is not None:
+    if first_stage == "multivec":
+        _, cand = mv.search(q_vecs, k_cand, allow=allow)
+    elif impact is not None:
         from .lexical import sparse_hybrid_search
         _, cand = sparse_hybrid_search(store, impact, qd, q_sparse, k_cand, fusion=fusion, allow=allow,
                                        mask_key=mask_key)

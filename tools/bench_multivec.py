@@ -27,6 +27,12 @@ of the rows removed, at stage_bytes 16 / 64 / 256 MiB.  The call's wall time (it
 written once, over that time, next to the copy yardstick counted the same way (a staged chunk moves its
 bytes twice, so its ceiling is half the yardstick); and the chunks and tokens the schedule sends down each
 path, from the planner's restatement in tests/mv_snapshot_ref.py.
+--search runs part 4 alone and writes profiles/multivec_search_bench.json: sr_mv_search_dev (DESIGN.md
+"Whole-corpus MaxSim search") on the index of part 1 (rows of 256 tokens) at dims 128 and 1024, fp16 and fp8,
+Lq 32, k 100, B 1 / 32 / 256: (a) the call's wall time and the scan and selection kernels' own times from the
+profiler's events, (b) the composition available without it, sr_mv_score_rows_dev over all rows in calls of
+K = 1024 plus torch.topk, on the same index in the same process, (c) the copy yardstick.  The scan's bytes
+are pool bytes x ceil(B / Q) per 64-token query block.
 """
 import argparse
 import json
@@ -229,6 +235,69 @@ def bench_compact(a, copy_gbs):
     return out
 
 
+# (dim, Lq, k) x B of the whole-corpus search table
+SEARCH_SHAPES = [(128, 32, 100), (1024, 32, 100)]
+SEARCH_B = [1, 32, 256]
+SCAN_KERNEL = {"fp16": "maxsim_scan", "fp8": "maxsim_scan_fp8"}
+
+
+def bench_search(a, copy_gbs):
+    """sr_mv_search_dev against the composition the library offered before it (sr_mv_score_rows_dev over
+    all rows in calls of K = 1024, then torch.topk), on the same index in the same process."""
+    from super_rag_amd.multivec import search_group_queries
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(0)
+    Ld, out = 256, []
+    for dim, Lq, k in SEARCH_SHAPES:
+        n = a.pool_tokens // Ld
+        Q = search_group_queries(dim)
+        xs = {d: NativeMultiVectorIndex(dim, dtype=d) for d in ("fp16", "fp8")}
+        step = max(1, (1 << 28) // (Ld * dim * 2))
+        for i in range(0, n, step):
+            m = min(step, n - i)
+            toks = unit_rows((m, Ld, dim), gen)
+            lens = torch.full((m,), Ld, dtype=torch.int32, device="cuda")
+            for x in xs.values():
+                x.add_dev(toks, lens)
+        for B in SEARCH_B:
+            q = unit_rows((B, Lq, dim), gen)
+            qlen = torch.full((B,), Lq, dtype=torch.int32, device="cuda")
+            chunks = [torch.arange(r0, min(n, r0 + 1024), dtype=torch.int64, device="cuda").repeat(B, 1).contiguous()
+                      for r0 in range(0, n, 1024)]
+            for d, x in xs.items():
+                res = (torch.empty((B, k), dtype=torch.float32, device="cuda"),
+                       torch.empty((B, k), dtype=torch.int64, device="cuda"))
+
+                def composed():
+                    s = torch.cat([x.score_rows_dev(q, qlen, r) for r in chunks], dim=1)
+                    return torch.topk(s, k, dim=1)
+
+                ms = median_ms(lambda: x.search_dev(q, qlen, k, out=res), a.repeats)
+                kn = kernel_ms(lambda: x.search_dev(q, qlen, k, out=res), (SCAN_KERNEL[d], "mv_topk"), a.repeats)
+                cm = median_ms(composed, a.repeats)
+                top = composed()
+                same = bool((top.values == res[0]).all().item())
+                blocks = (Lq + 63) // 64
+                groups = (B + Q - 1) // Q
+                nbytes = float(x.nbytes) * groups * blocks
+                scan = kn[SCAN_KERNEL[d]]
+                out.append({"dtype": d, "dim": dim, "B": B, "Lq": Lq, "k": k, "rows": n, "Ld": Ld, "Q": Q,
+                            "search_ms": round(ms[0], 4), "search_min_max_ms": [round(ms[1], 4), round(ms[2], 4)],
+                            "scan_kernel_ms": None if scan is None else round(scan, 4),
+                            "topk_kernel_ms": None if kn["mv_topk"] is None else round(kn["mv_topk"], 4),
+                            "composed_ms": round(cm[0], 4), "composed_min_max_ms": [round(cm[1], 4), round(cm[2], 4)],
+                            "search_over_composed": round(ms[0] / cm[0], 3),
+                            "scan_bytes": nbytes, "pool_bytes": x.nbytes, "query_groups": groups,
+                            "scan_GBs": round(nbytes / (ms[0] * 1e-3) / 1e9, 1),
+                            "scan_fraction_of_copy": round(nbytes / (ms[0] * 1e-3) / 1e9 / copy_gbs, 3),
+                            "scan_kernel_GBs": None if not scan else round(nbytes / (scan * 1e-3) / 1e9, 1),
+                            "scores_equal_composed": same})
+                print("# search", out[-1], flush=True)
+        for x in xs.values():
+            x.close()
+    return out
+
+
 def bench_forward(a):
     from super_rag_amd.encoder import MODELS, Encoder, random_weights
     spec = replace(MODELS["bge-m3"], vocab_size=a.vocab)
@@ -271,11 +340,16 @@ def main():
                     help="token storage of the index; both: fp16 and fp8 over the same tokens, compared")
     ap.add_argument("--compact", action="store_true",
                     help="part 3 alone: sr_mv_compact, to profiles/multivec_compact_bench.json")
+    ap.add_argument("--search", action="store_true",
+                    help="part 4 alone: sr_mv_search_dev against score_rows_dev + topk, to "
+                         "profiles/multivec_search_bench.json")
     ap.add_argument("--out", default=None,
                     help="default profiles/multivec_bench.json, profiles/multivec_fp8_bench.json with --dtype both")
     a = ap.parse_args()
     if a.out is None and a.compact:
         a.out = os.path.join(ROOT, "profiles", "multivec_compact_bench.json")
+    if a.out is None and a.search:
+        a.out = os.path.join(ROOT, "profiles", "multivec_search_bench.json")
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", "multivec_fp8_bench.json" if a.dtype == "both" else "multivec_bench.json")
     os.environ.setdefault("SUPER_RAG_AMD_SYNTHETIC", "1")
@@ -288,6 +362,11 @@ def main():
         rec["metric"] = "sr_mv_compact call time and moved bytes per second against the copy yardstick"
         rec["statistic"] = "median of repeats after one warm-up, each on a freshly rebuilt index"
         rec["compact"] = bench_compact(a, copy_gbs)
+    elif a.search:
+        rec["metric"] = ("sr_mv_search_dev (whole-corpus MaxSim top-k) against sr_mv_score_rows_dev over all rows + "
+                         "torch.topk, and its pool bytes per second against the copy yardstick")
+        rec["dtype"] = "both"
+        rec["search"] = bench_search(a, copy_gbs)
     else:
         rec["maxsim"] = bench_maxsim(a, copy_gbs)
         if not a.skip_encoder:
